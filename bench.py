@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HNSW build seconds + QPS@recall@10 on 1M x vector(768) L2 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one search pass of the hot path over one batch of --queries synthetic queries with its complete
 results on the host (get_scan_items + amgettuple semantics, ef_search = --efs, k = 10).  Consecutive steps take
@@ -14,6 +14,12 @@ replica of the graph; the BUILD is what the ranks share: each lock-step batch of
 the ranks and the results are all-gathered over RCCL, see pgvector-rx_amd/dist_build.py).
 
 Prints ONE JSON line (rank 0).  Inputs are synthetic and resident in HBM before any timed region.
+
+A plain run measures only the headline: build, warm-up, the K timed steps, recall@10 of their results.  --full adds what takes runs of
+its own: K1 on the resident table and on a vector(1536) table, the 2x / 4x query-batch and ef_search 40 / 200 sweeps, the CPU baseline
+(the --no-* options leave single legs out of a --full run).  --dump-outputs DIR writes the results of the last timed step as the caller
+of the scan receives them (rank 0): DIR/tids.npy, element_ids.npy, counts.npy (float64), distances.npy (float32) and query_rows.npy,
+the queries written (all of them up to 64 MB, past that a fixed seeded sample).
 """
 import argparse
 import json
@@ -60,7 +66,31 @@ def parse():
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="gloo = rehearsal of the multi-rank build with CPU-side exchange (several ranks may share one GPU)")
     p.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="also the legs that take runs of their own: K1 micro-benchmarks, query-batch and ef_search sweeps, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/<name>.npy (rank 0)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, res):
+    """The last timed step's (tids, distances, element ids, counts) as float64 / float32 .npy files.  Past DUMP_MAX_BYTES, a fixed seeded
+    sample of the queries (sorted; their indices in query_rows.npy) is written instead."""
+    tids, dists, els, cnt = res
+    nq, k = tids.shape
+    rows = np.arange(nq)
+    per_query = 8 + k * (8 + 4 + 8) + 8
+    if nq * per_query > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_MAX_BYTES // per_query, replace=False))
+    os.makedirs(d, exist_ok=True)
+    for name, arr in (("tids", tids[rows].astype(np.float64)), ("distances", dists[rows].astype(np.float32)),
+                      ("element_ids", els[rows].astype(np.float64)), ("counts", cnt[rows].astype(np.float64)),
+                      ("query_rows", rows.astype(np.float64))):
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def synth(n, dim, dist, seed, device, centres=None):
@@ -284,11 +314,13 @@ def run(a, json_fd):
     scan_stat = eng.kernel_stats(5)
     search_prof = ix.profile()
     qps = world * a.queries * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, results[(a.steps - 1) % S])
 
     # the batched L2 kernel of the lock-step placement (K1 k_dist_groups: query parked in LDS, coalesced row streaming,
     # shuffle reduction) on the same resident table, at a lock-step-sized launch: 32768 expansions x 32 rows
     k1 = None
-    if rank == 0:
+    if rank == 0 and a.full:
         rng = np.random.default_rng(5)
         g_n, per = 32768, 2 * a.m
         gq = rng.integers(0, a.rows, g_n).astype(np.uint32)
@@ -338,7 +370,7 @@ def run(a, json_fd):
     # the same scan at larger query batches: a launch costs a fixed ~2 ms (the drain of its last round of searches, one search long) on top of
     # ~0.7 us per query, so the rate of the kernel itself shows at batches that amortise it
     sweep = None
-    if rank == 0 and not a.no_query_sweep:
+    if rank == 0 and a.full and not a.no_query_sweep:
         sweep = []
         big, _ = synth(4 * a.queries, a.dim, a.dist, 99, dev, centres)
         for nq in (2 * a.queries, 4 * a.queries):
@@ -367,7 +399,7 @@ def run(a, json_fd):
 
     # BASELINE.md C2 lists ef_search 40 / 100 / 200: the same pipelined steps at the other two operating points
     efs_sweep = None
-    if rank == 0 and not a.no_efs_sweep:
+    if rank == 0 and a.full and not a.no_efs_sweep:
         efs_sweep = []
         for efs in (40, 200):
             if efs == a.efs:
@@ -468,7 +500,7 @@ def run(a, json_fd):
 
     # ---- CPU baseline: the oracle (scalar restatement of the reference) on this box's host cores, 1 thread ----
     cpu = None
-    if not a.no_cpu and world == 1:
+    if a.full and not a.no_cpu and world == 1:
         from oracle import orc
         # search baseline: the scalar scan on the SAME graph the device built
         all_rows = rows.cpu().numpy()
