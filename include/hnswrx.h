@@ -151,8 +151,40 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
 /* Accumulated since the last reset, while timing is enabled: kind 0 = query-vs-rows kernel (units =
  * distances), kind 1 = pair-block kernel (units = pairs), 2 = traversal kernel, 3 = back-link kernels, 4 = MFMA pair kernel (units = pairs),
  * 5 = pipelined scans (hx_index_search_submit): units = distances, ms = the UNION of the overlapping launches' busy intervals,
- * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16). */
+ * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16),
+ * 7 = exact scans (hx_exact_search): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls. */
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset);
+
+/* ---- exact k-NN scan: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k` ---------------------------------------------
+ * Per query, the first k rows of
+ *     SELECT row FROM rows[first_row, first_row + n_rows) WHERE row_pass ORDER BY row <op> query LIMIT k
+ * evaluated on the rows as stored.  A distance is the operator FUNCTION's float8 value (not the support function's), computed in the
+ * engine's canonical summation order (its l2sq / ip / l1 / popcount parts are the bits hx_distances returns for the pair):
+ *     HX_OP_L2      <->  sqrt((f64) l2sq)                                   vector.rs:586-593, halfvec.rs:751-763, sparsevec <->
+ *     HX_OP_NEG_IP  <#>  -(f64) ip  (a zero product gives -0.0)             vector.rs:624-633
+ *     HX_OP_COSINE  <=>  1 - clamp(s / sqrt((f64) na * (f64) nb), -1, 1)    vector.rs:541-556,638-647 (s, na, nb three f32 sums; NaN stays
+ *                        NaN: a zero vector gives 0/0); sparsevec: f32 norms over the stored values
+ *     HX_OP_L1      <+>  (f64) l1                                           vector.rs:652-659
+ *     HX_OP_HAMMING <~>  popcount(a ^ b)                                    bitvec.rs:144-153
+ *     HX_OP_JACCARD <%>  1 - ab / (aa + bb - ab), ab == 0 -> 1.0            bitvec.rs:113-132,158-167
+ * Any operator legal for the dtype may be used whatever metric the handle was created with (L2 / NEG_IP / COSINE / L1 for vector, halfvec
+ * and sparsevec; HAMMING / JACCARD for bit).  Rows a host normalised in place (cosine opclasses) are evaluated as normalised.
+ * Order: ascending under PostgreSQL's float8 comparison -- -0.0 == +0.0 (the value keeps its own sign), +inf before NaN, every NaN last and
+ * equal to every other NaN -- and equal values by ascending row id (the reference's bounded sort leaves their order unpinned).
+ *   queries   : the engine's query slots first_query .. first_query+nq-1 (hx_set_queries; upload WITHOUT normalize for <=>)
+ *   row_pass  : NULL = every row passes; else ceil(n_rows / 64) words, bit i % 64 of word i / 64 = row first_row + i passes.  Applies to all
+ *               nq queries; rows that fail are never read from HBM.
+ *   ids_out[q*k + j], dist_out[q*k + j]: the j-th row of query q and its distance; counts_out[q] = min(k, passing rows); entries past the
+ *               count are id 0xFFFFFFFF and distance NaN.  A NaN distance comes back as the default quiet NaN.
+ * HX_E_ARG: operator not legal for the dtype, k == 0 or k > HX_EXACT_MAX_K, a row range past hx_num_rows or past 2^32 - 1, a query range
+ * past the uploaded slots, NULL outputs.  Synchronous on the engine stream; reads only, so it may run while a pipelined index scan
+ * (hx_index_search_submit) is in flight.  The top-k scratch on the device is bounded independently of n_rows and nq (query blocks run in
+ * turn; HX_EXACT_SCRATCH bytes, default 256 MiB); a filtered call also keeps its bitmap (n_rows / 8 B) and the list of passing row ids
+ * (4 B each) there.  hx_kernel_stats kind 7 times the kernels only, not the bitmap upload. */
+enum hx_op { HX_OP_L2 = 0, HX_OP_NEG_IP = 1, HX_OP_COSINE = 2, HX_OP_L1 = 3, HX_OP_HAMMING = 4, HX_OP_JACCARD = 5 };
+#define HX_EXACT_MAX_K 1024
+int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                    const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Index: host-side mirror of the reference's graph functions, issuing the batches above

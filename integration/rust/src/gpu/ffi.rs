@@ -42,6 +42,14 @@ pub const HX_E_STATE: c_int = -6;
 pub const HX_QUERY_SLOT: u32 = 0x8000_0000;
 pub const HX_PAIR_MAX_ROWS: u32 = 64;
 pub const HX_PAGE_SIZE: usize = 8192;
+// hx_op: the SQL operator an exact scan orders by (hx_exact_search)
+pub const HX_OP_L2: c_int = 0; // <->
+pub const HX_OP_NEG_IP: c_int = 1; // <#>
+pub const HX_OP_COSINE: c_int = 2; // <=>
+pub const HX_OP_L1: c_int = 3; // <+>
+pub const HX_OP_HAMMING: c_int = 4; // <~>
+pub const HX_OP_JACCARD: c_int = 5; // <%>
+pub const HX_EXACT_MAX_K: u32 = 1024;
 
 #[link(name = "hnswrx")]
 extern "C" {
@@ -74,6 +82,9 @@ extern "C" {
     pub fn hx_set_timing(e: *mut hx_engine, enabled: c_int) -> c_int;
     pub fn hx_last_kernel_ms(e: *mut hx_engine, ms: *mut f32) -> c_int;
     pub fn hx_kernel_stats(e: *mut hx_engine, kind: c_int, launches: *mut u64, units: *mut u64, ms: *mut f64, reset: c_int) -> c_int;
+    // exact k-NN scan (the sequential-scan plan of ORDER BY v <op> q LIMIT k); op: HX_OP_* above
+    pub fn hx_exact_search(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, first_row: u64, n_rows: u64, row_pass: *const u64,
+                           k: u32, ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;
 
     // ---- index: the graph functions of src/graph/mod.rs, src/index/build.rs, scan.rs, insert.rs, vacuum.rs over the engine ----
     pub fn hx_index_create(e: *mut hx_engine, m: c_int, ef_construction: c_int, out: *mut *mut hx_index) -> c_int;

@@ -8,6 +8,8 @@ from . import build as _build
 
 F32, F16, BIT, SPARSE = 0, 1, 2, 3
 L2SQ, NEG_IP, L1, HAMMING, JACCARD = 0, 1, 2, 3, 4
+OP_L2, OP_NEG_IP, OP_COSINE, OP_L1, OP_HAMMING, OP_JACCARD = 0, 1, 2, 3, 4, 5   # hx_op: the SQL operators <-> <#> <=> <+> <~> <%>
+EXACT_MAX_K = 1024
 QUERY_SLOT = 0x80000000
 _NP = {F32: np.float32, F16: np.uint16, BIT: np.uint8, SPARSE: np.uint8}
 SPARSE_MAX_NNZ = 1000
@@ -80,6 +82,7 @@ def lib():
         "hx_set_timing": (i32, [vp, i32]),
         "hx_last_kernel_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "hx_kernel_stats": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), i32]),
+        "hx_exact_search": (i32, [vp, i32, u32, u32, u64, u64, vp, u32, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "hx_index_destroy": (i32, [vp]),
         "hx_index_last_error": (C.c_char_p, [vp]),
@@ -164,6 +167,7 @@ class Engine:
             raise HxError(rc, lib().hx_last_error(None).decode())
         self.h = h
         self.row_bytes = lib().hx_row_bytes(h)
+        self._nq = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -213,10 +217,12 @@ class Engine:
     def set_queries(self, q, normalize=False):
         a, n = self._rows(q)
         self._ck(lib().hx_set_queries(self.h, _p(a), n, int(normalize)))
+        self._nq = n
         return n
 
     def set_queries_device(self, dev_ptr, n, normalize=False):
         self._ck(lib().hx_set_queries_device(self.h, C.c_void_p(dev_ptr), n, int(normalize)))
+        self._nq = n
 
     def distances(self, query, row_ids):
         q, _ = self._rows(query)
@@ -276,6 +282,33 @@ class Engine:
 
     def set_timing(self, on=True):
         self._ck(lib().hx_set_timing(self.h, int(on)))
+
+    def exact_search(self, op, k, first_query=0, nq=None, first_row=0, n_rows=None, row_pass=None, packed=False):
+        """hx_exact_search: per query slot first_query.. (nq default: the rest of the uploaded slots), the k rows of [first_row, first_row + n_rows)
+        nearest under the SQL operator `op` (OP_*), exact float8 values, ties by row id.  row_pass: None (every row), a mask of n_rows entries
+        (bool or any integer type: non-zero passes; packed here), or with packed=True the uint64 words of the C bitmap as they are.
+        Returns (ids uint32[nq, k], dist float64[nq, k], counts uint32[nq]); padding is id 0xFFFFFFFF, NaN."""
+        nq = self._nq - first_query if nq is None else nq
+        n_rows = self.num_rows - first_row if n_rows is None else n_rows
+        n_words = (n_rows + 63) // 64
+        words = None
+        if row_pass is not None:
+            rp = np.asarray(row_pass)
+            if packed:
+                if rp.dtype != np.uint64 or rp.ndim != 1 or len(rp) < n_words:
+                    raise ValueError("packed row_pass needs ceil(n_rows / 64) uint64 words")
+                words = np.ascontiguousarray(rp)
+            else:
+                if rp.ndim != 1 or len(rp) != n_rows:
+                    raise ValueError("row_pass needs one entry per row")
+                bits = np.zeros(n_words * 64, np.uint8)
+                bits[:n_rows] = rp != 0
+                words = np.ascontiguousarray(np.packbits(bits, bitorder="little").view(np.uint64))
+        ids = np.empty((nq, k), np.uint32)
+        dist = np.empty((nq, k), np.float64)
+        cnt = np.empty(nq, np.uint32)
+        self._ck(lib().hx_exact_search(self.h, op, first_query, nq, first_row, n_rows, _p(words), k, _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
 
     def kernel_stats(self, kind, reset=False):
         l, u, ms = C.c_uint64(), C.c_uint64(), C.c_double()

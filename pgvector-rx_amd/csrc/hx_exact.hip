@@ -1,0 +1,457 @@
+// hx_exact.hip -- exact (filtered) k-NN scan on the device: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k`,
+// i.e. the executor calling the operator function on every heap row and keeping the top k (include/hnswrx.h: hx_exact_search).
+//
+// Values are the operator functions' float8 results, in the canonical summation order of hx_engine.hip:
+//   <->  sqrt((f64) l2sq)                                vector.rs:586-593, halfvec.rs:751-763, sparsevec <->
+//   <#>  -(f64) ip                                       vector.rs:624-633
+//   <=>  1 - clamp(s / sqrt((f64) na * (f64) nb), -1, 1) vector.rs:541-556,638-647 (three f32 accumulators; NaN stays NaN)
+//   <+>  (f64) l1                                        vector.rs:652-659
+//   <~>  (f64) popcount(a ^ b)                           bitvec.rs:144-153
+//   <%>  jaccard, ab == 0 -> 1.0                         bitvec.rs:113-132,158-167
+// The support-function parts (l2sq, ip, l1, popcounts) are the OpXxx operators of hx_ops.h with K1's lane mapping, so each is the very
+// value hx_distances returns for that pair; the cosine norms are the same sums with both operands the row (or the query).
+//
+// Order: ascending by the value under PostgreSQL's float8 comparison (-0.0 == +0.0, +inf < NaN, all NaNs equal), ties by ascending row id.
+// Each (value, id) is carried as a 64-bit order key (ex_key) and the id; the key is a bijection on values apart from the two zeros and the
+// NaN payloads, and ex_val inverts it (a zero is -0.0 exactly for <#>: its f32 sum starts at +0.0 and can never become -0.0).
+//
+// Pass 1 (k_exact_scan): workgroup (query tile of Q queries, row slice).  The Q queries are parked in LDS; each wave streams RIF row slots
+//   at a time (LPR lanes per row, 16-byte fragments, as K1) and evaluates every row fragment against every parked query, one accumulator
+//   per (row, query) -- a row is read from HBM once per tile.  Candidates that beat the running k-th entry of their query are appended to
+//   that query's buffer (global scratch, `cap` entries); after a round the workgroup sorts any buffer that could overflow in the next round
+//   and keeps its k best.  Pass 2 (k_exact_merge): one workgroup per query merges the slices' lists the same way in LDS.
+// Sparsevec rows: one lane per (query, row) pair with the merge joins of hx_sparse.hip, feeding the same top-k stage.
+// A filter bitmap is compacted into a row-id list on the device first (k_exact_compact); rows that fail it are never read.
+#include "hx_ops.h"
+
+namespace {
+
+constexpr int EX_WAVES = 4, EX_THREADS = EX_WAVES * 64, EX_MERGE_THREADS = 512;
+
+__device__ __forceinline__ uint64_t ex_key(double d)
+{
+    if (d != d) return ~0ull;                                  // every NaN: last, equal to every other NaN
+    if (d == 0.0) return 0x8000000000000000ull;                // -0.0 == +0.0
+    const uint64_t b = __builtin_bit_cast(uint64_t, d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ex_val(uint64_t key, bool neg_zero)
+{
+    if (key == ~0ull) return __builtin_bit_cast(double, 0x7ff8000000000000ull);
+    if (key == 0x8000000000000000ull) return neg_zero ? -0.0 : 0.0;
+    return __builtin_bit_cast(double, (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key);
+}
+__device__ __forceinline__ bool ex_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// bitonic sort of P (a power of two) entries in LDS by (key, id), by the whole workgroup
+__device__ void ex_sort(uint64_t *key, uint32_t *id, uint32_t P)
+{
+    for (uint32_t k2 = 2; k2 <= P; k2 <<= 1)
+        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
+                const uint32_t x = i ^ j;
+                if (x > i) {
+                    const uint64_t ka = key[i], kb = key[x];
+                    const uint32_t ia = id[i], ib = id[x];
+                    if (ex_less(kb, ib, ka, ia) == ((i & k2) == 0)) { key[i] = kb; key[x] = ka; id[i] = ib; id[x] = ia; }
+                }
+            }
+            __syncthreads();
+        }
+}
+__device__ __forceinline__ uint32_t ex_pow2(uint32_t n) { uint32_t p = 2; while (p < n) p <<= 1; return p; }
+
+// sorts the n entries in skey/sid (LDS), keeps the best min(n, k); *cnt / *thr_k / *thr_i updated.  Whole workgroup, uniform arguments.
+__device__ void ex_keep(uint64_t *skey, uint32_t *sid, uint32_t n, uint32_t k, uint32_t *cnt, uint64_t *thr_k, uint32_t *thr_i)
+{
+    const uint32_t P = ex_pow2(n);
+    for (uint32_t i = n + threadIdx.x; i < P; i += blockDim.x) { skey[i] = ~0ull; sid[i] = ~0u; }
+    __syncthreads();
+    ex_sort(skey, sid, P);
+    if (threadIdx.x == 0) {
+        const uint32_t m = n < k ? n : k;
+        *cnt = m;
+        if (m == k) { *thr_k = skey[k - 1]; *thr_i = sid[k - 1]; }
+    }
+    __syncthreads();
+}
+
+// one query's candidate buffer in global scratch: sort through LDS, keep the k best
+__device__ void ex_prune(uint64_t *gkey, uint32_t *gid, uint32_t stride, uint64_t *skey, uint32_t *sid, uint32_t k, uint32_t *cnt, uint64_t *thr_k, uint32_t *thr_i)
+{
+    const uint32_t n = *cnt;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) { skey[i] = gkey[(size_t)i * stride]; sid[i] = gid[(size_t)i * stride]; }
+    ex_keep(skey, sid, n, k, cnt, thr_k, thr_i);
+    const uint32_t m = *cnt;
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) { gkey[(size_t)i * stride] = skey[i]; gid[(size_t)i * stride] = sid[i]; }
+    __syncthreads();
+}
+
+// the f64 operator value from the lane partials (all lanes of the row's LPR-lane group get it)
+template <class OP, int HOP, int LPR>
+__device__ __forceinline__ double ex_value(const typename OP::acc_t &acc, float na, float nb)
+{
+    if constexpr (HOP == HX_OP_HAMMING) return (double)lanes_sum_i<LPR>(acc);
+    else if constexpr (HOP == HX_OP_JACCARD) {
+        const int ab = lanes_sum_i<LPR>(acc.ab), aa = lanes_sum_i<LPR>(acc.aa), bb = lanes_sum_i<LPR>(acc.bb);
+        return ab == 0 ? 1.0 : 1.0 - ((double)ab / (double)(aa + bb - ab));
+    } else {
+        const float s = lanes_sum_f<LPR>(acc);
+        if constexpr (HOP == HX_OP_L2) return sqrt((double)s);
+        else if constexpr (HOP == HX_OP_NEG_IP) return -(double)s;
+        else if constexpr (HOP == HX_OP_L1) return (double)s;
+        else {
+            double sim = (double)s / sqrt((double)na * (double)nb);
+            if (sim < -1.0) sim = -1.0;
+            if (sim > 1.0) sim = 1.0;                          // f64::clamp: NaN stays NaN
+            return 1.0 - sim;
+        }
+    }
+}
+
+struct ExArgs {
+    const uint8_t *rows, *queries; uint32_t pitch, cap_sp;   // cap_sp: sparsevec record capacity
+    uint32_t qslot0, nq;                                      // queries of this block: slots qslot0 .. qslot0 + nq - 1
+    const uint32_t *ids; uint32_t row0; uint32_t n, per;      // rows: ids[0..n) or row0 + [0..n); slice s = [s * per, (s + 1) * per)
+    uint32_t S, k, cap;
+    uint64_t *gkey; uint32_t *gid, *gcnt;                     // [query tile][slice][cap][Q], [query][slice]
+};
+
+// Q queries x one row slice.  RPS = 64 / LPR rows per wave slot; a round is EX_WAVES * RIF slots.
+template <class OP, int HOP, int LPR, int RIF, int Q>
+__global__ void __launch_bounds__(EX_THREADS)
+k_exact_scan(const ExArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t *q_lds = lds;
+    uint64_t *skey = (uint64_t *)(lds + (size_t)Q * a.pitch);
+    uint32_t *sid = (uint32_t *)(skey + a.cap);
+    __shared__ uint64_t thr_k[Q];
+    __shared__ uint32_t thr_i[Q], cnt[Q];
+    __shared__ float qn[Q];
+    constexpr bool kCos = HOP == HX_OP_COSINE, kSp = OP::kSparse;
+    constexpr int RPS = 64 / LPR, R = EX_WAVES * RIF * RPS;
+    const uint32_t tile = blockIdx.x, s = blockIdx.y;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, sub = lane / LPR, sl = lane % LPR;
+
+    for (int i = 0; i < Q; i++) {
+        const uint32_t qi = tile * Q + i < a.nq ? tile * Q + i : a.nq - 1;   // a partial tile re-reads the last query; never appended
+        const uint8_t *src = a.queries + (size_t)(a.qslot0 + qi) * a.pitch;
+        for (uint32_t o = threadIdx.x * 16u; o < a.pitch; o += EX_THREADS * 16u) *(u4 *)(q_lds + o * Q + i * 16) = *(const u4 *)(src + o);
+    }
+    if (threadIdx.x < Q) {                                     // a query past the block gets a threshold nothing beats
+        const bool live = tile * Q + threadIdx.x < a.nq;
+        thr_k[threadIdx.x] = live ? ~0ull : 0ull; thr_i[threadIdx.x] = live ? ~0u : 0u; cnt[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    if constexpr (kCos) {                                      // |q|^2 in the canonical order (the row's is formed with its dot products)
+        for (int i = wave; i < Q; i += EX_WAVES) {
+            float v = 0.0f;
+            if constexpr (kSp) {
+                if (lane == 0) { const SpRow r = sp_row((const uint8_t *)q_lds, a.cap_sp); for (int t = 0; t < r.nnz; t++) v += r.val[t] * r.val[t]; }
+            } else {
+                typename OP::acc_t acc; OP::init(acc);
+                for (uint32_t c = lane * 16u; c < a.pitch; c += 1024u) { const u4 x = *(const u4 *)(q_lds + c * Q + i * 16); OP::add(acc, x, x); }
+                v = lanes_sum_f<64>(acc);
+            }
+            if (lane == 0) qn[i] = v;
+        }
+        __syncthreads();
+    }
+
+    const uint32_t beg = s * a.per, end = beg + a.per < a.n ? beg + a.per : a.n;
+    uint64_t *gkey = a.gkey + ((size_t)tile * a.S + s) * a.cap * Q;      // entry pos of query i at [pos * Q + i]
+    uint32_t *gid = a.gid + ((size_t)tile * a.S + s) * a.cap * Q;
+    for (uint32_t b = beg; b < end; b += R) {
+        uint32_t rid[RIF]; bool ok[RIF]; const uint8_t *rp[RIF];
+#pragma unroll
+        for (int j = 0; j < RIF; j++) {
+            const uint32_t r = b + (wave * RIF + j) * RPS + sub;
+            ok[j] = r < end;
+            rid[j] = a.ids ? a.ids[ok[j] ? r : beg] : a.row0 + (ok[j] ? r : beg);   // slots past the slice re-read its first row; never appended
+            rp[j] = a.rows + (size_t)rid[j] * a.pitch;
+        }
+        auto append = [&](int i, int j, double v) {            // lanes sl == 0 hold the row's values
+            const uint64_t key = ex_key(v);
+            if (sl == 0 && ok[j] && ex_less(key, rid[j], thr_k[i], thr_i[i])) {
+                const uint32_t pos = atomicAdd(&cnt[i], 1u);
+                gkey[pos * Q + i] = key; gid[pos * Q + i] = rid[j];
+            }
+        };
+        if constexpr (kSp) {
+            static_assert(LPR == 1 && RIF == 1 && Q == 1, "sparsevec: one lane per pair");
+            const SpRow q = sp_row((const uint8_t *)q_lds, a.cap_sp), r = sp_row(rp[0], a.cap_sp);
+            constexpr int K = HOP == HX_OP_L2 ? K_L2 : HOP == HX_OP_L1 ? K_L1 : K_IP;
+            const float v = sp_merge<K>(q, r);                 // -ip for K_IP
+            double dv;
+            if constexpr (HOP == HX_OP_L2) dv = sqrt((double)v);
+            else if constexpr (HOP == HX_OP_NEG_IP || HOP == HX_OP_L1) dv = (double)v;
+            else {                                             // sparsevec_cosine_distance: f32 norms over the stored values
+                float na = 0.0f;
+                for (int t = 0; t < r.nnz; t++) na += r.val[t] * r.val[t];
+                double sim = (double)(-v) / sqrt((double)qn[0] * (double)na);
+                if (sim < -1.0) sim = -1.0;
+                if (sim > 1.0) sim = 1.0;
+                dv = 1.0 - sim;
+            }
+            append(0, 0, dv);
+        } else {
+            typename OP::acc_t acc[RIF][Q];
+            float nacc[RIF];
+#pragma unroll
+            for (int j = 0; j < RIF; j++) {
+                nacc[j] = 0.0f;
+#pragma unroll
+                for (int i = 0; i < Q; i++) OP::init(acc[j][i]);
+            }
+            for (uint32_t c = sl * 16u; c < a.pitch; c += LPR * 16u) {
+                u4 rv[RIF];
+#pragma unroll
+                for (int j = 0; j < RIF; j++) rv[j] = *(const u4 *)(rp[j] + c);
+                if constexpr (kCos) {
+#pragma unroll
+                    for (int j = 0; j < RIF; j++) OP::add(nacc[j], rv[j], rv[j]);
+                }
+#pragma unroll
+                for (int i = 0; i < Q; i++) {
+                    const u4 qv = *(const u4 *)(q_lds + c * Q + i * 16);
+#pragma unroll
+                    for (int j = 0; j < RIF; j++) OP::add(acc[j][i], qv, rv[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < RIF; j++) {
+                const float na = kCos ? lanes_sum_f<LPR>(nacc[j]) : 0.0f;
+#pragma unroll
+                for (int i = 0; i < Q; i++) append(i, j, ex_value<OP, HOP, LPR>(acc[j][i], na, kCos ? qn[i] : 0.0f));
+            }
+        }
+        __syncthreads();
+        for (int i = 0; i < Q; i++)                            // a buffer that the next round could overflow is cut back to k
+            if (cnt[i] > a.cap - R) ex_prune(gkey + i, gid + i, Q, skey, sid, a.k, &cnt[i], &thr_k[i], &thr_i[i]);
+        __syncthreads();                                       // every thread has read the counts before the next round appends
+    }
+    for (int i = 0; i < Q; i++) {
+        if (tile * Q + i >= a.nq) break;
+        if (cnt[i] > a.k) ex_prune(gkey + i, gid + i, Q, skey, sid, a.k, &cnt[i], &thr_k[i], &thr_i[i]);
+        if (threadIdx.x == 0) a.gcnt[(size_t)(tile * Q + i) * a.S + s] = cnt[i];
+    }
+}
+
+// one workgroup per query: the S slice lists (each <= k entries, at stride cap) in chunks of cap2 / 2 positions through an LDS buffer
+__global__ void __launch_bounds__(EX_MERGE_THREADS)
+k_exact_merge(const uint64_t *__restrict__ gkey, const uint32_t *__restrict__ gid, const uint32_t *__restrict__ gcnt, uint32_t S, uint32_t cap, uint32_t Q,
+              uint32_t k, uint32_t cap2, int neg_zero, uint32_t *__restrict__ ids_out, double *__restrict__ dist_out, uint32_t *__restrict__ cnt_out)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint64_t *skey = (uint64_t *)lds;
+    uint32_t *sid = (uint32_t *)(skey + cap2);
+    __shared__ uint64_t thr_k; __shared__ uint32_t thr_i, cnt;
+    const uint32_t q = blockIdx.x, C = cap2 / 2;
+    if (threadIdx.x == 0) { thr_k = ~0ull; thr_i = ~0u; cnt = 0; }
+    __syncthreads();
+    const uint64_t total = (uint64_t)S * k;
+    for (uint64_t p0 = 0; p0 < total; p0 += C) {
+        for (uint32_t t = threadIdx.x; t < C && p0 + t < total; t += EX_MERGE_THREADS) {
+            const uint32_t s = (uint32_t)((p0 + t) / k), i = (uint32_t)((p0 + t) % k);
+            if (i >= gcnt[(size_t)q * S + s]) continue;
+            const size_t o = (((size_t)(q / Q) * S + s) * cap + i) * Q + q % Q;
+            const uint64_t key = gkey[o]; const uint32_t id = gid[o];
+            if (ex_less(key, id, thr_k, thr_i)) { const uint32_t pos = atomicAdd(&cnt, 1u); skey[pos] = key; sid[pos] = id; }
+        }
+        __syncthreads();
+        if (cnt > cap2 - C) ex_keep(skey, sid, cnt, k, &cnt, &thr_k, &thr_i);
+        __syncthreads();                                       // every thread has read cnt before the next chunk appends
+    }
+    if (cnt > 0) ex_keep(skey, sid, cnt, k, &cnt, &thr_k, &thr_i);
+    const uint32_t m = cnt;
+    for (uint32_t j = threadIdx.x; j < k; j += EX_MERGE_THREADS) {
+        ids_out[(size_t)q * k + j] = j < m ? sid[j] : 0xFFFFFFFFu;
+        dist_out[(size_t)q * k + j] = j < m ? ex_val(skey[j], neg_zero != 0) : __builtin_bit_cast(double, 0x7ff8000000000000ull);
+    }
+    if (threadIdx.x == 0) cnt_out[q] = m;
+}
+
+// filter bitmap -> row-id list (order free: the top-k order includes the id)
+__global__ void k_exact_compact(const uint64_t *__restrict__ words, uint64_t n_words, uint64_t n_rows, uint32_t row0, uint32_t *__restrict__ out, uint32_t *__restrict__ ctr)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    uint64_t bits = words[w];
+    if (w == n_words - 1 && (n_rows & 63)) bits &= (1ull << (n_rows & 63)) - 1;
+    if (!bits) return;
+    uint32_t pos = atomicAdd(ctr, (uint32_t)__popcll(bits));
+    while (bits) { const int b = __builtin_ctzll(bits); out[pos++] = row0 + (uint32_t)(w * 64 + b); bits &= bits - 1; }
+}
+
+struct ExPlan { uint32_t Q, R, cap, S, per, nqb, cap2; };
+
+template <class OP, int HOP, int LPR, int RIF, int Q>
+hipError_t ex_launch_scan(hx_engine *e, const ExArgs &a, uint32_t tiles)
+{
+    const size_t lds = (size_t)Q * a.pitch + (size_t)a.cap * 12;
+    static thread_local uint64_t attr_devices = 0;            // the attribute is per device: set it on each device this thread launches on
+    const uint64_t bit = 1ull << (e->device & 63);
+    if (lds > 65536 && !(attr_devices & bit)) {
+        hipError_t s = hipFuncSetAttribute((const void *)k_exact_scan<OP, HOP, LPR, RIF, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+        if (s != hipSuccess) return s;
+        attr_devices |= bit;
+    }
+    hipLaunchKernelGGL((k_exact_scan<OP, HOP, LPR, RIF, Q>), dim3(tiles, a.S), dim3(EX_THREADS), lds, e->stream, a);
+    return hipGetLastError();
+}
+
+// rows per round of a workgroup for (LPR, RIF): EX_WAVES * RIF * 64 / LPR
+template <class OP, int HOP, int LPR>
+hipError_t ex_dispatch_q(hx_engine *e, const ExArgs &a, uint32_t Q, uint32_t tiles)
+{
+    if (Q == 16) return ex_launch_scan<OP, HOP, LPR, 2, 16>(e, a, tiles);
+    if (Q == 4) return ex_launch_scan<OP, HOP, LPR, 4, 4>(e, a, tiles);
+    return ex_launch_scan<OP, HOP, LPR, 4, 1>(e, a, tiles);
+}
+template <class OP, int HOP>
+hipError_t ex_dispatch_lpr(hx_engine *e, const ExArgs &a, uint32_t Q, uint32_t tiles)
+{
+    return a.pitch > 128 ? ex_dispatch_q<OP, HOP, 64>(e, a, Q, tiles) : ex_dispatch_q<OP, HOP, 8>(e, a, Q, tiles);
+}
+template <template <int> class OPT>
+hipError_t ex_dispatch_float(hx_engine *e, int op, const ExArgs &a, uint32_t Q, uint32_t tiles)
+{
+    switch (op) {
+    case HX_OP_L2: return ex_dispatch_lpr<OPT<K_L2>, HX_OP_L2>(e, a, Q, tiles);
+    case HX_OP_NEG_IP: return ex_dispatch_lpr<OPT<K_IP>, HX_OP_NEG_IP>(e, a, Q, tiles);
+    case HX_OP_COSINE: return ex_dispatch_lpr<OPT<K_IP>, HX_OP_COSINE>(e, a, Q, tiles);
+    default: return ex_dispatch_lpr<OPT<K_L1>, HX_OP_L1>(e, a, Q, tiles);
+    }
+}
+template <int HOP>
+hipError_t ex_launch_sparse(hx_engine *e, const ExArgs &a, uint32_t tiles)
+{
+    hipLaunchKernelGGL((k_exact_scan<OpSparse<K_L2>, HOP, 1, 1, 1>), dim3(tiles, a.S), dim3(EX_THREADS), (size_t)a.pitch + (size_t)a.cap * 12, e->stream, a);
+    return hipGetLastError();
+}
+
+hipError_t ex_scan(hx_engine *e, int op, const ExArgs &a, uint32_t Q, uint32_t tiles)
+{
+    if (e->dtype == HX_F32) return ex_dispatch_float<OpF32>(e, op, a, Q, tiles);
+    if (e->dtype == HX_F16) return ex_dispatch_float<OpF16>(e, op, a, Q, tiles);
+    if (e->dtype == HX_BIT) return op == HX_OP_HAMMING ? ex_dispatch_lpr<OpHamming, HX_OP_HAMMING>(e, a, Q, tiles)
+                                                       : ex_dispatch_lpr<OpJaccard, HX_OP_JACCARD>(e, a, Q, tiles);
+    switch (op) {
+    case HX_OP_L2: return ex_launch_sparse<HX_OP_L2>(e, a, tiles);
+    case HX_OP_NEG_IP: return ex_launch_sparse<HX_OP_NEG_IP>(e, a, tiles);
+    case HX_OP_COSINE: return ex_launch_sparse<HX_OP_COSINE>(e, a, tiles);
+    default: return ex_launch_sparse<HX_OP_L1>(e, a, tiles);
+    }
+}
+
+} // namespace
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                               const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+{
+    if (!e) return HX_E_ARG;
+    const bool bit = e->dtype == HX_BIT;
+    if (op < HX_OP_L2 || op > HX_OP_JACCARD || bit != (op == HX_OP_HAMMING || op == HX_OP_JACCARD))
+        return e->fail(HX_E_ARG, "operator is not defined for this column type");
+    if (k == 0 || k > HX_EXACT_MAX_K) return e->fail(HX_E_ARG, "k must be in [1, HX_EXACT_MAX_K]");
+    if (first_row > e->n_rows || n_rows > e->n_rows - first_row) return e->fail(HX_E_ARG, "row range past the stored rows");
+    if (first_row + n_rows > 0xFFFFFFFFull) return e->fail(HX_E_ARG, "row range past 2^32 - 1");
+    if ((uint64_t)first_query + nq > e->n_queries) return e->fail(HX_E_ARG, "query range past the uploaded query slots");
+    if (!ids_out || !dist_out || !counts_out) return e->fail(HX_E_ARG, "NULL output");
+    if (nq == 0) return HX_OK;
+
+    const uint64_t n_words = (n_rows + 63) / 64;
+    uint64_t n_pass = n_rows;
+    if (row_pass) {
+        n_pass = 0;
+        for (uint64_t w = 0; w < n_words; w++) {
+            uint64_t b = row_pass[w];
+            if (w == n_words - 1 && (n_rows & 63)) b &= (1ull << (n_rows & 63)) - 1;
+            n_pass += (uint64_t)__builtin_popcountll(b);
+        }
+    }
+    if (n_pass == 0) {
+        for (size_t i = 0; i < (size_t)nq * k; i++) { ids_out[i] = 0xFFFFFFFFu; dist_out[i] = std::nan(""); }
+        memset(counts_out, 0, nq * sizeof(uint32_t));
+        return HX_OK;
+    }
+    HX_HIP(e, hipSetDevice(e->device));
+
+    // plan: query tile Q (LDS budget), rows per round R, per-(query, slice) buffer cap, slices S (~1024 workgroups), queries per block
+    const uint32_t pitch = (uint32_t)e->pitch;
+    ExPlan p{};
+    if (e->dtype == HX_SPARSE) { p.Q = 1; p.R = EX_WAVES * 64; }
+    else {
+        p.Q = nq >= 16 && 16ull * pitch <= 64 * 1024 ? 16 : nq >= 4 && 4ull * pitch <= 64 * 1024 ? 4 : 1;
+        const uint32_t rif = p.Q == 16 ? 2 : 4, lpr = pitch > 128 ? 64 : 8;
+        p.R = EX_WAVES * rif * (64 / lpr);
+    }
+    p.cap = 64; while (p.cap < 2 * k || p.cap < k + p.R) p.cap <<= 1;
+    p.cap2 = 4096; while (p.cap2 < 4 * k) p.cap2 <<= 1;
+    const uint32_t tiles_all = (nq + p.Q - 1) / p.Q;
+    p.S = std::max<uint64_t>(1, std::min<uint64_t>((1024 + tiles_all - 1) / tiles_all, (n_pass + 4 * p.R - 1) / (4 * p.R)));
+    p.per = (uint32_t)((n_pass + p.S - 1) / p.S);
+    p.S = (uint32_t)((n_pass + p.per - 1) / p.per);
+    // top-k scratch per query: S buffers of cap entries + S counts + the merged output; bounded by HX_EXACT_SCRATCH bytes (default 256 MiB).
+    // A filtered call also holds its bitmap (n_rows / 8 B) and the compacted id list (4 B per passing row) on the device.
+    uint64_t budget = 256ull << 20;
+    if (const char *env = getenv("HX_EXACT_SCRATCH")) budget = std::max<uint64_t>(1, strtoull(env, nullptr, 10));
+    const uint64_t per_q = (uint64_t)p.S * p.cap * 12 + (uint64_t)p.S * 4 + (uint64_t)k * 12 + 4;
+    p.nqb = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(p.Q, budget / per_q / p.Q * p.Q));
+
+    const size_t ids_bytes = row_pass ? al16((size_t)n_pass * 4) : 0, words_bytes = row_pass ? al16((size_t)n_words * 8) : 0;
+    const size_t o_words = ids_bytes, o_ctr = o_words + words_bytes, o_key = o_ctr + 16;
+    const size_t nq_pad = (size_t)(p.nqb + p.Q - 1) / p.Q * p.Q;            // the buffers are laid out by whole query tiles
+    const size_t o_id = o_key + al16(nq_pad * p.S * p.cap * 8), o_cnt = o_id + al16(nq_pad * p.S * p.cap * 4);
+    const size_t o_oid = o_cnt + al16((size_t)p.nqb * p.S * 4), o_od = o_oid + al16((size_t)p.nqb * k * 4), o_oc = o_od + al16((size_t)p.nqb * k * 8);
+    const size_t need = o_oc + al16((size_t)p.nqb * 4);
+    if (need > e->cap_exact) {
+        if (e->d_exact) (void)hipFree(e->d_exact);
+        e->d_exact = nullptr; e->cap_exact = 0;
+        if (hipMalloc((void **)&e->d_exact, need) != hipSuccess) return e->fail(HX_E_NOMEM, "cannot reserve exact-scan scratch in HBM");
+        e->cap_exact = need;
+    }
+    uint8_t *d = e->d_exact;
+    uint32_t *d_ids = row_pass ? (uint32_t *)d : nullptr;
+    uint64_t launches = 0; double ms = 0.0;
+    if (row_pass) {
+        HX_HIP(e, hipMemsetAsync(d + o_ctr, 0, 4, e->stream));
+        HX_HIP(e, hipMemcpyAsync(d + o_words, row_pass, n_words * 8, hipMemcpyHostToDevice, e->stream));
+    }
+    if (e->timing) HX_HIP(e, hipEventRecord(e->ev0, e->stream));   // kind 7 = kernel time: the bitmap upload is not in it
+    if (row_pass) {
+        hipLaunchKernelGGL(k_exact_compact, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, e->stream,
+                           (const uint64_t *)(d + o_words), n_words, n_rows, (uint32_t)first_row, d_ids, (uint32_t *)(d + o_ctr));
+        HX_HIP(e, hipGetLastError());
+        launches++;
+    }
+    ExArgs a{};
+    a.rows = e->d_rows; a.queries = e->d_queries; a.pitch = pitch; a.cap_sp = (uint32_t)std::min(e->dim, HX_SPARSE_MAX_NNZ);
+    a.ids = d_ids; a.row0 = (uint32_t)first_row; a.n = (uint32_t)n_pass; a.per = p.per; a.S = p.S; a.k = k; a.cap = p.cap;
+    a.gkey = (uint64_t *)(d + o_key); a.gid = (uint32_t *)(d + o_id); a.gcnt = (uint32_t *)(d + o_cnt);
+    for (uint32_t q0 = 0; q0 < nq; q0 += p.nqb) {
+        const uint32_t nb = std::min(p.nqb, nq - q0);
+        if (q0 > 0 && e->timing) HX_HIP(e, hipEventRecord(e->ev0, e->stream));
+        a.qslot0 = first_query + q0; a.nq = nb;
+        HX_HIP(e, ex_scan(e, op, a, p.Q, (nb + p.Q - 1) / p.Q));
+        hipLaunchKernelGGL(k_exact_merge, dim3(nb), dim3(EX_MERGE_THREADS), (size_t)p.cap2 * 12, e->stream, a.gkey, a.gid, a.gcnt, p.S, p.cap, p.Q, k, p.cap2,
+                           (int)(op == HX_OP_NEG_IP), (uint32_t *)(d + o_oid), (double *)(d + o_od), (uint32_t *)(d + o_oc));
+        HX_HIP(e, hipGetLastError());
+        launches += 2;
+        if (e->timing) HX_HIP(e, hipEventRecord(e->ev1, e->stream));
+        HX_HIP(e, hipMemcpyAsync(ids_out + (size_t)q0 * k, d + o_oid, (size_t)nb * k * 4, hipMemcpyDeviceToHost, e->stream));
+        HX_HIP(e, hipMemcpyAsync(dist_out + (size_t)q0 * k, d + o_od, (size_t)nb * k * 8, hipMemcpyDeviceToHost, e->stream));
+        HX_HIP(e, hipMemcpyAsync(counts_out + q0, d + o_oc, (size_t)nb * 4, hipMemcpyDeviceToHost, e->stream));
+        HX_HIP(e, hipStreamSynchronize(e->stream));
+        if (e->timing) { float t = 0.f; HX_HIP(e, hipEventElapsedTime(&t, e->ev0, e->ev1)); ms += t; }
+    }
+    if (e->timing) {
+        e->last_ms = (float)ms;
+        e->stat_exact.launches += launches; e->stat_exact.units += n_pass * nq; e->stat_exact.ms += ms;
+    }
+    return HX_OK;
+}
