@@ -152,7 +152,8 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
  * distances), kind 1 = pair-block kernel (units = pairs), 2 = traversal kernel, 3 = back-link kernels, 4 = MFMA pair kernel (units = pairs),
  * 5 = pipelined scans (hx_index_search_submit): units = distances, ms = the UNION of the overlapping launches' busy intervals,
  * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16),
- * 7 = exact scans (hx_exact_search): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls. */
+ * 7 = exact scans (hx_exact_search): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
+ * 8 = range scans (hx_exact_range): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls. */
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset);
 
 /* ---- exact k-NN scan: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k` ---------------------------------------------
@@ -185,6 +186,36 @@ enum hx_op { HX_OP_L2 = 0, HX_OP_NEG_IP = 1, HX_OP_COSINE = 2, HX_OP_L1 = 3, HX_
 #define HX_EXACT_MAX_K 1024
 int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
                     const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
+
+/* ---- exact range scan: the sequential-scan plans of `WHERE v <op> q < r` and `WHERE v <op> q < r ORDER BY v <op> q` (no LIMIT) ----------
+ * Per query slot first_query + i, every row of
+ *     SELECT row FROM rows[first_row, first_row + n_rows) WHERE row_pass AND (row <op> query) <cmp> radius[i]
+ * Value: op, the query slots, the row range and row_pass mean exactly what they mean for hx_exact_search, and a row's value is the same
+ *   operator-function float8 in the canonical summation order, bit for bit the value hx_exact_search returns for it.
+ * Predicate: PostgreSQL's float8 comparison (float8lt / le / gt / ge): -0.0 equals +0.0; every NaN equals every other NaN and is greater
+ *   than everything else, +inf included.  So `v <=> q > 0.5` includes the rows whose value is NaN, `< NaN` returns every row whose value is
+ *   not NaN, and `<= NaN` every row.  radius[i] belongs to query first_query + i (a host with one SQL constant repeats it).
+ * Output (CSR): offsets_out[0..nq] (nq + 1 entries); the rows of query i are ids_out[offsets_out[i] .. offsets_out[i+1]) and dist_out
+ *   holds their values at the same positions.  HX_RANGE_BY_ROW lists them by ascending row id (the heap order of the seq scan);
+ *   HX_RANGE_BY_DISTANCE ascending under the float8 order, ties by ascending row id (the ORDER BY without LIMIT).  A NaN value comes back
+ *   as the default quiet NaN, as in hx_exact_search.
+ * Count only: ids_out == NULL && dist_out == NULL fills offsets_out and *total_out only (SELECT count(*) ...; sizing the output); cap is
+ *   not used then.  dist_out == NULL alone returns the ids without values.
+ * Capacity: *total_out is always the true total.  If it exceeds cap the call returns HX_E_NOMEM ("capacity exceeded"); offsets_out and
+ *   *total_out are still filled and the contents of ids_out / dist_out are unspecified.
+ * Device memory: bounded by HX_RANGE_SCRATCH bytes (default 256 MiB, at least 64 KiB) whatever n_rows, nq and the number of hits are:
+ *   query blocks and windows of the output run in turn.  One exception: under HX_RANGE_BY_DISTANCE one query's hits must fit the output
+ *   window; when they do not, the call returns HX_E_NOMEM with the counts filled.  A filtered call also keeps its bitmap (n_rows / 8 B),
+ *   its per-word offsets (n_rows / 16 B) and the list of passing row ids (4 B each) on the device, as hx_exact_search does.
+ * HX_E_ARG: an operator not legal for the dtype, cmp or order out of range, radius NULL with nq > 0, offsets_out or total_out NULL,
+ *   ids_out NULL with dist_out not NULL, and the row-range and query-range errors of hx_exact_search.
+ * Synchronous on the engine stream; reads only, so it may run while a pipelined index scan (hx_index_search_submit) is in flight.
+ * hx_kernel_stats kind 8 times it: units = distances evaluated, ms = summed kernel time (not the uploads and copies); kind 7 is untouched. */
+enum hx_cmp { HX_CMP_LT = 0, HX_CMP_LE = 1, HX_CMP_GT = 2, HX_CMP_GE = 3 };     /* v <op> q  <  <=  >  >=  radius */
+enum hx_range_order { HX_RANGE_BY_ROW = 0, HX_RANGE_BY_DISTANCE = 1 };
+int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
+                   uint64_t first_row, uint64_t n_rows, const uint64_t *row_pass, int order, uint64_t cap,
+                   uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Index: host-side mirror of the reference's graph functions, issuing the batches above

@@ -50,6 +50,14 @@ pub const HX_OP_L1: c_int = 3; // <+>
 pub const HX_OP_HAMMING: c_int = 4; // <~>
 pub const HX_OP_JACCARD: c_int = 5; // <%>
 pub const HX_EXACT_MAX_K: u32 = 1024;
+// hx_cmp: the comparison of a range scan, v <op> q <cmp> radius (hx_exact_range)
+pub const HX_CMP_LT: c_int = 0; // <
+pub const HX_CMP_LE: c_int = 1; // <=
+pub const HX_CMP_GT: c_int = 2; // >
+pub const HX_CMP_GE: c_int = 3; // >=
+// hx_range_order: heap order (WHERE only) or the ORDER BY without LIMIT
+pub const HX_RANGE_BY_ROW: c_int = 0;
+pub const HX_RANGE_BY_DISTANCE: c_int = 1;
 
 #[link(name = "hnswrx")]
 extern "C" {
@@ -85,6 +93,10 @@ extern "C" {
     // exact k-NN scan (the sequential-scan plan of ORDER BY v <op> q LIMIT k); op: HX_OP_* above
     pub fn hx_exact_search(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, first_row: u64, n_rows: u64, row_pass: *const u64,
                            k: u32, ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;
+    // exact range scan (the sequential-scan plans of WHERE v <op> q < r, with or without ORDER BY v <op> q); cmp: HX_CMP_*, order: HX_RANGE_BY_*
+    pub fn hx_exact_range(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64, n_rows: u64,
+                          row_pass: *const u64, order: c_int, cap: u64, offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64,
+                          total_out: *mut u64) -> c_int;
 
     // ---- index: the graph functions of src/graph/mod.rs, src/index/build.rs, scan.rs, insert.rs, vacuum.rs over the engine ----
     pub fn hx_index_create(e: *mut hx_engine, m: c_int, ef_construction: c_int, out: *mut *mut hx_index) -> c_int;

@@ -10,6 +10,9 @@ F32, F16, BIT, SPARSE = 0, 1, 2, 3
 L2SQ, NEG_IP, L1, HAMMING, JACCARD = 0, 1, 2, 3, 4
 OP_L2, OP_NEG_IP, OP_COSINE, OP_L1, OP_HAMMING, OP_JACCARD = 0, 1, 2, 3, 4, 5   # hx_op: the SQL operators <-> <#> <=> <+> <~> <%>
 EXACT_MAX_K = 1024
+CMP_LT, CMP_LE, CMP_GT, CMP_GE = 0, 1, 2, 3           # hx_cmp: v <op> q  <  <=  >  >=  radius
+RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap order, or the ORDER BY without LIMIT
+E_NOMEM = -3
 QUERY_SLOT = 0x80000000
 _NP = {F32: np.float32, F16: np.uint16, BIT: np.uint8, SPARSE: np.uint8}
 SPARSE_MAX_NNZ = 1000
@@ -83,6 +86,7 @@ def lib():
         "hx_last_kernel_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "hx_kernel_stats": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), i32]),
         "hx_exact_search": (i32, [vp, i32, u32, u32, u64, u64, vp, u32, vp, vp, vp]),
+        "hx_exact_range": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, vp, i32, u64, vp, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "hx_index_destroy": (i32, [vp]),
         "hx_index_last_error": (C.c_char_p, [vp]),
@@ -154,6 +158,24 @@ def _p(a):
 
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _row_words(row_pass, n_rows, packed):
+    """A row filter as the C bitmap: None; a mask of n_rows entries (bool or any integer type: non-zero passes), packed here; or with
+    packed=True the uint64 words as they are (ceil(n_rows / 64) of them)."""
+    if row_pass is None:
+        return None
+    n_words = (n_rows + 63) // 64
+    rp = np.asarray(row_pass)
+    if packed:
+        if rp.dtype != np.uint64 or rp.ndim != 1 or len(rp) < n_words:
+            raise ValueError("packed row_pass needs ceil(n_rows / 64) uint64 words")
+        return np.ascontiguousarray(rp)
+    if rp.ndim != 1 or len(rp) != n_rows:
+        raise ValueError("row_pass needs one entry per row")
+    bits = np.zeros(n_words * 64, np.uint8)
+    bits[:n_rows] = rp != 0
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view(np.uint64))
 
 
 class Engine:
@@ -290,25 +312,45 @@ class Engine:
         Returns (ids uint32[nq, k], dist float64[nq, k], counts uint32[nq]); padding is id 0xFFFFFFFF, NaN."""
         nq = self._nq - first_query if nq is None else nq
         n_rows = self.num_rows - first_row if n_rows is None else n_rows
-        n_words = (n_rows + 63) // 64
-        words = None
-        if row_pass is not None:
-            rp = np.asarray(row_pass)
-            if packed:
-                if rp.dtype != np.uint64 or rp.ndim != 1 or len(rp) < n_words:
-                    raise ValueError("packed row_pass needs ceil(n_rows / 64) uint64 words")
-                words = np.ascontiguousarray(rp)
-            else:
-                if rp.ndim != 1 or len(rp) != n_rows:
-                    raise ValueError("row_pass needs one entry per row")
-                bits = np.zeros(n_words * 64, np.uint8)
-                bits[:n_rows] = rp != 0
-                words = np.ascontiguousarray(np.packbits(bits, bitorder="little").view(np.uint64))
+        words = _row_words(row_pass, n_rows, packed)
         ids = np.empty((nq, k), np.uint32)
         dist = np.empty((nq, k), np.float64)
         cnt = np.empty(nq, np.uint32)
         self._ck(lib().hx_exact_search(self.h, op, first_query, nq, first_row, n_rows, _p(words), k, _p(ids), _p(dist), _p(cnt)))
         return ids, dist, cnt
+
+    def exact_range(self, op, radius, cmp=CMP_LT, first_query=0, nq=None, first_row=0, n_rows=None, row_pass=None, packed=False,
+                    ordered=False, count_only=False, cap=None):
+        """hx_exact_range: per query slot first_query.. (nq default: the rest of the uploaded slots), every row of [first_row, first_row + n_rows)
+        whose value under the SQL operator `op` (OP_*) satisfies `value <cmp> radius` (CMP_*, PostgreSQL's float8 comparison: -0.0 == +0.0,
+        NaN above everything).  radius: a scalar or one value per query.  row_pass: as in exact_search.  ordered: by value, ties by row id
+        (RANGE_BY_DISTANCE), else by row id (RANGE_BY_ROW).  Returns (offsets uint64[nq + 1], ids uint32[total], dist float64[total]), CSR:
+        query i's rows are ids[offsets[i]:offsets[i + 1]]; count_only: the arrays are empty.  cap=None: one call with a default capacity,
+        then, if the hits exceed it, one more sized to the total."""
+        nq = self._nq - first_query if nq is None else nq
+        n_rows = self.num_rows - first_row if n_rows is None else n_rows
+        words = _row_words(row_pass, n_rows, packed)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (nq,)))
+        offsets = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64()
+        order = RANGE_BY_DISTANCE if ordered else RANGE_BY_ROW
+        L = lib()
+        if count_only:
+            self._ck(L.hx_exact_range(self.h, op, cmp, _p(r), first_query, nq, first_row, n_rows, _p(words), order, 0, _p(offsets), None, None,
+                                      C.byref(total)))
+            return offsets, np.empty(0, np.uint32), np.empty(0, np.float64)
+        n = max(1 << 16, 64 * nq) if cap is None else int(cap)
+        for attempt in range(2):
+            ids, dist = np.empty(max(n, 1), np.uint32), np.empty(max(n, 1), np.float64)
+            rc = L.hx_exact_range(self.h, op, cmp, _p(r), first_query, nq, first_row, n_rows, _p(words), order, n, _p(offsets), _p(ids), _p(dist),
+                                  C.byref(total))
+            if rc == E_NOMEM and cap is None and attempt == 0 and total.value > n:
+                n = total.value                              # sized to the total exactly: the second and last call
+                continue
+            self._ck(rc)
+            break
+        t = int(total.value)
+        return offsets, ids[:t], dist[:t]
 
     def kernel_stats(self, kind, reset=False):
         l, u, ms = C.c_uint64(), C.c_uint64(), C.c_double()

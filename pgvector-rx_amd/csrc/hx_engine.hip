@@ -475,7 +475,7 @@ int hx_destroy(hx_engine *e)
     HxMirror &mr = e->mirror;
     void *hp[] = {c.h_req, c.h_res, mr.h_stage, mr.io.h_io, mr.h_lk, e->grp.h_ctr, e->grp.h, e->bw.h, e->bw.h_ctr};
     void *dp[] = {c.d_req, c.d_res, e->d_rows, e->d_queries, mr.d_l0_ids, mr.d_l0_d, mr.d_l0_cnt, mr.d_level, mr.d_up_block, mr.d_up_ids, mr.d_up_d, mr.d_up_cnt, mr.io.d_vis, mr.d_stage, mr.io.d_io, mr.d_lk, mr.d_pm, mr.d_pm_valid, mr.io.d_spill,
-                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact};
+                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact, e->d_range};
     for (void *p : hp) if (p) (void)hipHostFree(p);
     for (void *p : dp) if (p) (void)hipFree(p);
     for (HxFusedIo &io : e->scan_io) {                           // pipelined scan slots: a launch still in flight is drained first
@@ -800,7 +800,7 @@ int hx_last_kernel_ms(hx_engine *e, float *ms) { if (!e || !ms) return HX_E_ARG;
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset)
 {
     if (!e) return HX_E_ARG;
-    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : e->stat_mfma;
+    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : kind == 8 ? e->stat_range : e->stat_mfma;
     if (kind == 5 && reset) { e->scan_epoch_set = false; e->scan_last_end = 0.0; }
     if (launches) *launches = s.launches;
     if (units) *units = s.units;

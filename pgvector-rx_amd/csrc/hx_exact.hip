@@ -1,19 +1,10 @@
 // hx_exact.hip -- exact (filtered) k-NN scan on the device: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k`,
 // i.e. the executor calling the operator function on every heap row and keeping the top k (include/hnswrx.h: hx_exact_search).
 //
-// Values are the operator functions' float8 results, in the canonical summation order of hx_engine.hip:
-//   <->  sqrt((f64) l2sq)                                vector.rs:586-593, halfvec.rs:751-763, sparsevec <->
-//   <#>  -(f64) ip                                       vector.rs:624-633
-//   <=>  1 - clamp(s / sqrt((f64) na * (f64) nb), -1, 1) vector.rs:541-556,638-647 (three f32 accumulators; NaN stays NaN)
-//   <+>  (f64) l1                                        vector.rs:652-659
-//   <~>  (f64) popcount(a ^ b)                           bitvec.rs:144-153
-//   <%>  jaccard, ab == 0 -> 1.0                         bitvec.rs:113-132,158-167
-// The support-function parts (l2sq, ip, l1, popcounts) are the OpXxx operators of hx_ops.h with K1's lane mapping, so each is the very
-// value hx_distances returns for that pair; the cosine norms are the same sums with both operands the row (or the query).
+// Values, the order key and the row streaming (ex_park / ex_eval) are those of hx_exact_core.h, shared with the range scans.
 //
 // Order: ascending by the value under PostgreSQL's float8 comparison (-0.0 == +0.0, +inf < NaN, all NaNs equal), ties by ascending row id.
-// Each (value, id) is carried as a 64-bit order key (ex_key) and the id; the key is a bijection on values apart from the two zeros and the
-// NaN payloads, and ex_val inverts it (a zero is -0.0 exactly for <#>: its f32 sum starts at +0.0 and can never become -0.0).
+// Each (value, id) is carried as the 64-bit order key (ex_key) and the id.
 //
 // Pass 1 (k_exact_scan): workgroup (query tile of Q queries, row slice).  The Q queries are parked in LDS; each wave streams RIF row slots
 //   at a time (LPR lanes per row, 16-byte fragments, as K1) and evaluates every row fragment against every parked query, one accumulator
@@ -22,25 +13,12 @@
 //   and keeps its k best.  Pass 2 (k_exact_merge): one workgroup per query merges the slices' lists the same way in LDS.
 // Sparsevec rows: one lane per (query, row) pair with the merge joins of hx_sparse.hip, feeding the same top-k stage.
 // A filter bitmap is compacted into a row-id list on the device first (k_exact_compact); rows that fail it are never read.
-#include "hx_ops.h"
+#include "hx_exact_core.h"
 
 namespace {
 
-constexpr int EX_WAVES = 4, EX_THREADS = EX_WAVES * 64, EX_MERGE_THREADS = 512;
+constexpr int EX_MERGE_THREADS = 512;
 
-__device__ __forceinline__ uint64_t ex_key(double d)
-{
-    if (d != d) return ~0ull;                                  // every NaN: last, equal to every other NaN
-    if (d == 0.0) return 0x8000000000000000ull;                // -0.0 == +0.0
-    const uint64_t b = __builtin_bit_cast(uint64_t, d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ex_val(uint64_t key, bool neg_zero)
-{
-    if (key == ~0ull) return __builtin_bit_cast(double, 0x7ff8000000000000ull);
-    if (key == 0x8000000000000000ull) return neg_zero ? -0.0 : 0.0;
-    return __builtin_bit_cast(double, (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key);
-}
 __device__ __forceinline__ bool ex_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
 
 // bitonic sort of P (a power of two) entries in LDS by (key, id), by the whole workgroup
@@ -87,28 +65,6 @@ __device__ void ex_prune(uint64_t *gkey, uint32_t *gid, uint32_t stride, uint64_
     __syncthreads();
 }
 
-// the f64 operator value from the lane partials (all lanes of the row's LPR-lane group get it)
-template <class OP, int HOP, int LPR>
-__device__ __forceinline__ double ex_value(const typename OP::acc_t &acc, float na, float nb)
-{
-    if constexpr (HOP == HX_OP_HAMMING) return (double)lanes_sum_i<LPR>(acc);
-    else if constexpr (HOP == HX_OP_JACCARD) {
-        const int ab = lanes_sum_i<LPR>(acc.ab), aa = lanes_sum_i<LPR>(acc.aa), bb = lanes_sum_i<LPR>(acc.bb);
-        return ab == 0 ? 1.0 : 1.0 - ((double)ab / (double)(aa + bb - ab));
-    } else {
-        const float s = lanes_sum_f<LPR>(acc);
-        if constexpr (HOP == HX_OP_L2) return sqrt((double)s);
-        else if constexpr (HOP == HX_OP_NEG_IP) return -(double)s;
-        else if constexpr (HOP == HX_OP_L1) return (double)s;
-        else {
-            double sim = (double)s / sqrt((double)na * (double)nb);
-            if (sim < -1.0) sim = -1.0;
-            if (sim > 1.0) sim = 1.0;                          // f64::clamp: NaN stays NaN
-            return 1.0 - sim;
-        }
-    }
-}
-
 struct ExArgs {
     const uint8_t *rows, *queries; uint32_t pitch, cap_sp;   // cap_sp: sparsevec record capacity
     uint32_t qslot0, nq;                                      // queries of this block: slots qslot0 .. qslot0 + nq - 1
@@ -129,35 +85,16 @@ k_exact_scan(const ExArgs a)
     __shared__ uint64_t thr_k[Q];
     __shared__ uint32_t thr_i[Q], cnt[Q];
     __shared__ float qn[Q];
-    constexpr bool kCos = HOP == HX_OP_COSINE, kSp = OP::kSparse;
     constexpr int RPS = 64 / LPR, R = EX_WAVES * RIF * RPS;
     const uint32_t tile = blockIdx.x, s = blockIdx.y;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, sub = lane / LPR, sl = lane % LPR;
 
-    for (int i = 0; i < Q; i++) {
-        const uint32_t qi = tile * Q + i < a.nq ? tile * Q + i : a.nq - 1;   // a partial tile re-reads the last query; never appended
-        const uint8_t *src = a.queries + (size_t)(a.qslot0 + qi) * a.pitch;
-        for (uint32_t o = threadIdx.x * 16u; o < a.pitch; o += EX_THREADS * 16u) *(u4 *)(q_lds + o * Q + i * 16) = *(const u4 *)(src + o);
-    }
-    if (threadIdx.x < Q) {                                     // a query past the block gets a threshold nothing beats
-        const bool live = tile * Q + threadIdx.x < a.nq;
-        thr_k[threadIdx.x] = live ? ~0ull : 0ull; thr_i[threadIdx.x] = live ? ~0u : 0u; cnt[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    if constexpr (kCos) {                                      // |q|^2 in the canonical order (the row's is formed with its dot products)
-        for (int i = wave; i < Q; i += EX_WAVES) {
-            float v = 0.0f;
-            if constexpr (kSp) {
-                if (lane == 0) { const SpRow r = sp_row((const uint8_t *)q_lds, a.cap_sp); for (int t = 0; t < r.nnz; t++) v += r.val[t] * r.val[t]; }
-            } else {
-                typename OP::acc_t acc; OP::init(acc);
-                for (uint32_t c = lane * 16u; c < a.pitch; c += 1024u) { const u4 x = *(const u4 *)(q_lds + c * Q + i * 16); OP::add(acc, x, x); }
-                v = lanes_sum_f<64>(acc);
-            }
-            if (lane == 0) qn[i] = v;
+    ex_park<OP, HOP, Q>(a.queries, a.qslot0, a.nq, tile, a.pitch, a.cap_sp, q_lds, qn, [&] {   // a partial tile's extra queries: never appended
+        if (threadIdx.x < Q) {                                 // a query past the block gets a threshold nothing beats
+            const bool live = tile * Q + threadIdx.x < a.nq;
+            thr_k[threadIdx.x] = live ? ~0ull : 0ull; thr_i[threadIdx.x] = live ? ~0u : 0u; cnt[threadIdx.x] = 0;
         }
-        __syncthreads();
-    }
+    });
 
     const uint32_t beg = s * a.per, end = beg + a.per < a.n ? beg + a.per : a.n;
     uint64_t *gkey = a.gkey + ((size_t)tile * a.S + s) * a.cap * Q;      // entry pos of query i at [pos * Q + i]
@@ -178,54 +115,7 @@ k_exact_scan(const ExArgs a)
                 gkey[pos * Q + i] = key; gid[pos * Q + i] = rid[j];
             }
         };
-        if constexpr (kSp) {
-            static_assert(LPR == 1 && RIF == 1 && Q == 1, "sparsevec: one lane per pair");
-            const SpRow q = sp_row((const uint8_t *)q_lds, a.cap_sp), r = sp_row(rp[0], a.cap_sp);
-            constexpr int K = HOP == HX_OP_L2 ? K_L2 : HOP == HX_OP_L1 ? K_L1 : K_IP;
-            const float v = sp_merge<K>(q, r);                 // -ip for K_IP
-            double dv;
-            if constexpr (HOP == HX_OP_L2) dv = sqrt((double)v);
-            else if constexpr (HOP == HX_OP_NEG_IP || HOP == HX_OP_L1) dv = (double)v;
-            else {                                             // sparsevec_cosine_distance: f32 norms over the stored values
-                float na = 0.0f;
-                for (int t = 0; t < r.nnz; t++) na += r.val[t] * r.val[t];
-                double sim = (double)(-v) / sqrt((double)qn[0] * (double)na);
-                if (sim < -1.0) sim = -1.0;
-                if (sim > 1.0) sim = 1.0;
-                dv = 1.0 - sim;
-            }
-            append(0, 0, dv);
-        } else {
-            typename OP::acc_t acc[RIF][Q];
-            float nacc[RIF];
-#pragma unroll
-            for (int j = 0; j < RIF; j++) {
-                nacc[j] = 0.0f;
-#pragma unroll
-                for (int i = 0; i < Q; i++) OP::init(acc[j][i]);
-            }
-            for (uint32_t c = sl * 16u; c < a.pitch; c += LPR * 16u) {
-                u4 rv[RIF];
-#pragma unroll
-                for (int j = 0; j < RIF; j++) rv[j] = *(const u4 *)(rp[j] + c);
-                if constexpr (kCos) {
-#pragma unroll
-                    for (int j = 0; j < RIF; j++) OP::add(nacc[j], rv[j], rv[j]);
-                }
-#pragma unroll
-                for (int i = 0; i < Q; i++) {
-                    const u4 qv = *(const u4 *)(q_lds + c * Q + i * 16);
-#pragma unroll
-                    for (int j = 0; j < RIF; j++) OP::add(acc[j][i], qv, rv[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < RIF; j++) {
-                const float na = kCos ? lanes_sum_f<LPR>(nacc[j]) : 0.0f;
-#pragma unroll
-                for (int i = 0; i < Q; i++) append(i, j, ex_value<OP, HOP, LPR>(acc[j][i], na, kCos ? qn[i] : 0.0f));
-            }
-        }
+        ex_eval<OP, HOP, LPR, RIF, Q>(q_lds, qn, rp, a.pitch, a.cap_sp, sl, append);
         __syncthreads();
         for (int i = 0; i < Q; i++)                            // a buffer that the next round could overflow is cut back to k
             if (cnt[i] > a.cap - R) ex_prune(gkey + i, gid + i, Q, skey, sid, a.k, &cnt[i], &thr_k[i], &thr_i[i]);

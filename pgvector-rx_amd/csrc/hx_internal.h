@@ -121,6 +121,7 @@ struct hx_engine {
     bool timing = false; float last_ms = 0.f;
     HxKernelStat stat_dist, stat_pair, stat_fused, stat_links, stat_mfma, stat_wsel;
     HxKernelStat stat_exact; uint8_t *d_exact = nullptr; size_t cap_exact = 0;   // exact scans (hx_exact.hip): kind 7 counters, device scratch
+    HxKernelStat stat_range; uint8_t *d_range = nullptr; size_t cap_range = 0;   // range scans (hx_range.hip): kind 8 counters, device scratch
     // pipelined scans: launches overlap, so their busy time is the UNION of the launches' [start, end] intervals (HIP events of each slot's stream,
     // measured from ev_scan_epoch on the engine's stream); stat_scan.ms = that union
     HxKernelStat stat_scan; hipEvent_t ev_scan_epoch = nullptr; bool scan_epoch_set = false; double scan_last_end = 0.0;
