@@ -58,7 +58,8 @@ enum hx_status {
     HX_E_NOMEM = -3,    /* host or device allocation failed / capacity exceeded */
     HX_E_HIP = -4,      /* a HIP runtime call failed */
     HX_E_NODEVICE = -5, /* no usable GPU: the engine never falls back to the CPU */
-    HX_E_STATE = -6     /* call sequence error */
+    HX_E_STATE = -6,    /* call sequence error */
+    HX_E_RANGE = -7     /* a value out of range for the target type ("<v>" is out of range for type halfvec, halfvec.rs:665) */
 };
 
 typedef struct hx_engine hx_engine;   /* device row store + kernels (replaces DistanceFn, graph/mod.rs:144-145) */
@@ -78,6 +79,15 @@ const char *hx_last_error(const hx_engine *e);     /* e may be NULL: error of th
  * front in HBM (the reference's Vec<u8> arena, build.rs:249, grows instead).  Fails with
  * HX_E_NODEVICE when no GPU is visible. */
 int hx_create(int device, int dtype, int metric, int dim, uint64_t capacity_rows, hx_engine **out);
+/* hx_create with flags; flags == 0 is exactly hx_create, an unknown flag is HX_E_ARG.
+ * HX_CREATE_SCAN_ONLY: an engine for the sequential-scan plans and re-ranking, never indexed.  HX_F32 and HX_F16 then accept up to
+ *   16000 dimensions (VECTOR_MAX_DIM vector.rs:30, HALFVEC_MAX_DIM halfvec.rs:28; HX_E_DIM "vector cannot have more than 16000 dimensions"
+ *   above); HX_BIT and HX_SPARSE keep hx_create's limits.  The row store (hx_append_rows*, hx_pop_rows, hx_read_rows, hx_normalize_rows),
+ *   the query slots (hx_set_queries*), hx_distances, hx_exact_search, hx_exact_range, hx_exact_rerank and the halfvec casts work at every
+ *   legal dim; hx_index_create, hx_distances_batch, hx_pairwise*, hx_rows_equal return HX_E_STATE.  Argument checks run before any device
+ *   is touched, as in hx_create. */
+#define HX_CREATE_SCAN_ONLY 1
+int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_rows, int flags, hx_engine **out);
 int hx_destroy(hx_engine *e);
 
 int hx_dim(const hx_engine *e);
@@ -106,6 +116,19 @@ int hx_normalize_rows(hx_engine *e, uint64_t first, uint64_t n, double *norms_ho
  * with normalize!=0 they are normalised first (scan.rs:749-751). */
 int hx_set_queries(hx_engine *e, const void *queries_host, uint32_t nq, int normalize);
 int hx_set_queries_device(hx_engine *e, const void *queries_dev, uint32_t nq, int normalize);
+
+/* ---- casts vector -> halfvec, device to device: `embedding::halfvec(n)` (vector_to_halfvec, halfvec.rs:644-670) --------------------------
+ * src is an HX_F32 engine, dst an HX_F16 engine (either may be scan-only) on the same device (else HX_E_ARG) with the same dim (else
+ * HX_E_DIM "expected <dst dim> dimensions, not <src dim>").  Every element is f32_to_half (halfvec.rs:92-143) bit for bit -- not IEEE
+ * conversion: |x| < 2^-24 goes to zero below 2^-25 (exp < 103), a NaN keeps mant >> 13 (at least 1) as its payload.  A finite element whose
+ * half is +-inf fails the whole call with HX_E_RANGE and changes nothing in dst (row count, rows, queries); hx_last_error(dst) holds the
+ * reference's message and names the source row (or query slot) and element.  +-inf elements are not errors.  HX_E_STATE while a pipelined
+ * scan slot of dst is busy (hx_index_search_submit without its wait).  hx_kernel_stats kind 10 times the cast kernels (units = elements).
+ *   hx_append_rows_halfvec: appends the casts of src rows [first, first + n) to dst, as hx_append_rows_device would (capacity, first_row_id).
+ *   hx_set_queries_halfvec: replaces dst's query slots with the casts of all of src's uploaded query slots; normalize as in hx_set_queries
+ *                           on a halfvec engine (l2_normalize_raw of the cast values). */
+int hx_append_rows_halfvec(hx_engine *dst, const hx_engine *src, uint64_t first, uint64_t n, uint64_t *first_row_id);
+int hx_set_queries_halfvec(hx_engine *dst, const hx_engine *src, int normalize);
 
 /* One query vector (host) against n rows: the batched form of the <=2M FunctionCall2Coll calls of one
  * candidate expansion (graph/mod.rs:205-224, scan.rs:362-383).  out[i] = d(query, row_ids[i]). */
@@ -153,7 +176,9 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
  * 5 = pipelined scans (hx_index_search_submit): units = distances, ms = the UNION of the overlapping launches' busy intervals,
  * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16),
  * 7 = exact scans (hx_exact_search): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
- * 8 = range scans (hx_exact_range): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls. */
+ * 8 = range scans (hx_exact_range): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
+ * 9 = exact re-rank (hx_exact_rerank): units = distances evaluated (candidates listed), ms = the summed kernel time of the calls,
+ * 10 = vector -> halfvec casts (hx_append_rows_halfvec, hx_set_queries_halfvec): units = elements cast. */
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset);
 
 /* ---- exact k-NN scan: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k` ---------------------------------------------
@@ -216,6 +241,23 @@ enum hx_range_order { HX_RANGE_BY_ROW = 0, HX_RANGE_BY_DISTANCE = 1 };
 int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
                    uint64_t first_row, uint64_t n_rows, const uint64_t *row_pass, int order, uint64_t cap,
                    uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
+
+/* ---- exact re-rank of per-query candidate lists: the outer `ORDER BY v <op> q LIMIT k` over a subquery's rows ----------------------------
+ * Per query slot first_query + i, the first k rows of
+ *     SELECT row FROM (cand_ids[cand_offsets[i] .. cand_offsets[i+1])) ORDER BY row <op> query LIMIT k
+ * (the re-rank of a halfvec expression index's candidates on the full-precision vector column: INTEGRATION.md §3c).
+ * op, the legal dtype x operator pairs, values, order and output layout are exactly hx_exact_search's: a value is bit for bit the one
+ *   hx_exact_search returns for that (query, row); float8 order, -0.0 == +0.0, NaN last; ties by ascending row id; counts_out[i] =
+ *   min(k, list length); entries past the count are id 0xFFFFFFFF and NaN.
+ * A list is a multiset: an id listed twice is a row listed twice, and both copies sit next to each other in the output.  Lists may be
+ *   empty and have no length limit.
+ * HX_E_ARG: an operator not legal for the dtype, k == 0 or k > HX_EXACT_MAX_K, an id >= hx_num_rows, cand_offsets[0] != 0 or decreasing
+ *   offsets, a query range past the uploaded slots, a NULL output (or NULL offsets; NULL cand_ids with a non-empty list).
+ * Device memory stays within HX_EXACT_SCRATCH bytes (default 256 MiB) whatever nq and the list lengths are: candidates are uploaded and
+ *   query blocks run in windows.  Synchronous on the engine stream; reads only, so it may run while a pipelined index scan is in flight.
+ *   hx_kernel_stats kind 9 times it (units = distances evaluated, ms = summed kernel time, not the uploads); kinds 7 and 8 are untouched. */
+int hx_exact_rerank(hx_engine *e, int op, uint32_t first_query, uint32_t nq, const uint64_t *cand_offsets, const uint32_t *cand_ids,
+                    uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Index: host-side mirror of the reference's graph functions, issuing the batches above

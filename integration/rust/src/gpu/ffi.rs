@@ -38,6 +38,7 @@ pub const HX_E_NOMEM: c_int = -3;
 pub const HX_E_HIP: c_int = -4;
 pub const HX_E_NODEVICE: c_int = -5;
 pub const HX_E_STATE: c_int = -6;
+pub const HX_E_RANGE: c_int = -7; // "<v>" is out of range for type halfvec (halfvec.rs:665)
 
 pub const HX_QUERY_SLOT: u32 = 0x8000_0000;
 pub const HX_PAIR_MAX_ROWS: u32 = 64;
@@ -58,6 +59,8 @@ pub const HX_CMP_GE: c_int = 3; // >=
 // hx_range_order: heap order (WHERE only) or the ORDER BY without LIMIT
 pub const HX_RANGE_BY_ROW: c_int = 0;
 pub const HX_RANGE_BY_DISTANCE: c_int = 1;
+// hx_create_ex flags: an engine for the scan plans and re-ranking only (vector / halfvec up to 16000 dims, no index)
+pub const HX_CREATE_SCAN_ONLY: c_int = 1;
 
 #[link(name = "hnswrx")]
 extern "C" {
@@ -66,6 +69,8 @@ extern "C" {
 
     // ---- engine: device row store + batched distance kernels (replaces graph::DistanceFn, src/graph/mod.rs:144-145) ----
     pub fn hx_create(device: c_int, dtype: c_int, metric: c_int, dim: c_int, capacity_rows: u64, out: *mut *mut hx_engine) -> c_int;
+    pub fn hx_create_ex(device: c_int, dtype: c_int, metric: c_int, dim: c_int, capacity_rows: u64, flags: c_int,
+                        out: *mut *mut hx_engine) -> c_int;
     pub fn hx_destroy(e: *mut hx_engine) -> c_int;
     pub fn hx_dim(e: *const hx_engine) -> c_int;
     pub fn hx_row_bytes(e: *const hx_engine) -> u64;
@@ -78,6 +83,9 @@ extern "C" {
     pub fn hx_normalize_rows(e: *mut hx_engine, first: u64, n: u64, norms_host: *mut f64) -> c_int;
     pub fn hx_set_queries(e: *mut hx_engine, queries_host: *const c_void, nq: u32, normalize: c_int) -> c_int;
     pub fn hx_set_queries_device(e: *mut hx_engine, queries_dev: *const c_void, nq: u32, normalize: c_int) -> c_int;
+    // casts vector -> halfvec, device to device (embedding::halfvec(n)); HX_E_RANGE leaves dst unchanged
+    pub fn hx_append_rows_halfvec(dst: *mut hx_engine, src: *const hx_engine, first: u64, n: u64, first_row_id: *mut u64) -> c_int;
+    pub fn hx_set_queries_halfvec(dst: *mut hx_engine, src: *const hx_engine, normalize: c_int) -> c_int;
     pub fn hx_distances(e: *mut hx_engine, query_host: *const c_void, row_ids: *const u32, n: u32, out: *mut f32) -> c_int;
     pub fn hx_distances_batch(e: *mut hx_engine, n_groups: u32, group_query: *const u32, group_offsets: *const u32,
                               row_ids: *const u32, out: *mut f32) -> c_int;
@@ -97,6 +105,9 @@ extern "C" {
     pub fn hx_exact_range(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64, n_rows: u64,
                           row_pass: *const u64, order: c_int, cap: u64, offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64,
                           total_out: *mut u64) -> c_int;
+    // exact re-rank of per-query candidate lists (the outer ORDER BY v <op> q LIMIT k over an index scan's candidates)
+    pub fn hx_exact_rerank(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, cand_offsets: *const u64, cand_ids: *const u32, k: u32,
+                           ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;
 
     // ---- index: the graph functions of src/graph/mod.rs, src/index/build.rs, scan.rs, insert.rs, vacuum.rs over the engine ----
     pub fn hx_index_create(e: *mut hx_engine, m: c_int, ef_construction: c_int, out: *mut *mut hx_index) -> c_int;

@@ -13,6 +13,8 @@ EXACT_MAX_K = 1024
 CMP_LT, CMP_LE, CMP_GT, CMP_GE = 0, 1, 2, 3           # hx_cmp: v <op> q  <  <=  >  >=  radius
 RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap order, or the ORDER BY without LIMIT
 E_NOMEM = -3
+E_RANGE = -7                                           # a value out of range for the target type (the halfvec casts)
+CREATE_SCAN_ONLY = 1                                   # hx_create_ex: no index; vector / halfvec up to 16000 dims
 QUERY_SLOT = 0x80000000
 _NP = {F32: np.float32, F16: np.uint16, BIT: np.uint8, SPARSE: np.uint8}
 SPARSE_MAX_NNZ = 1000
@@ -64,6 +66,7 @@ def lib():
         "hx_abi_version": (i32, []),
         "hx_last_error": (C.c_char_p, [vp]),
         "hx_create": (i32, [i32, i32, i32, i32, u64, C.POINTER(vp)]),
+        "hx_create_ex": (i32, [i32, i32, i32, i32, u64, i32, C.POINTER(vp)]),
         "hx_destroy": (i32, [vp]),
         "hx_dim": (i32, [vp]),
         "hx_row_bytes": (u64, [vp]),
@@ -76,6 +79,8 @@ def lib():
         "hx_normalize_rows": (i32, [vp, u64, u64, vp]),
         "hx_set_queries": (i32, [vp, vp, u32, i32]),
         "hx_set_queries_device": (i32, [vp, vp, u32, i32]),
+        "hx_append_rows_halfvec": (i32, [vp, vp, u64, u64, C.POINTER(u64)]),
+        "hx_set_queries_halfvec": (i32, [vp, vp, i32]),
         "hx_distances": (i32, [vp, vp, vp, u32, vp]),
         "hx_distances_batch": (i32, [vp, u32, vp, vp, vp, vp]),
         "hx_pairwise": (i32, [vp, vp, u32, vp]),
@@ -87,6 +92,7 @@ def lib():
         "hx_kernel_stats": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), i32]),
         "hx_exact_search": (i32, [vp, i32, u32, u32, u64, u64, vp, u32, vp, vp, vp]),
         "hx_exact_range": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, vp, i32, u64, vp, vp, vp, vp]),
+        "hx_exact_rerank": (i32, [vp, i32, u32, u32, vp, vp, u32, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "hx_index_destroy": (i32, [vp]),
         "hx_index_last_error": (C.c_char_p, [vp]),
@@ -181,10 +187,12 @@ def _row_words(row_pass, n_rows, packed):
 class Engine:
     """hx_engine: device row store + batched distance kernels (replaces graph::DistanceFn)."""
 
-    def __init__(self, dtype, metric, dim, capacity, device=0):
+    def __init__(self, dtype, metric, dim, capacity, device=0, scan_only=False):
+        """scan_only: an engine for the scan plans and re-ranking (hx_create_ex HX_CREATE_SCAN_ONLY): vector / halfvec up to 16000 dims,
+        never indexed."""
         self.dtype, self.metric, self.dim = dtype, metric, dim
         h = C.c_void_p()
-        rc = lib().hx_create(device, dtype, metric, dim, int(capacity), C.byref(h))
+        rc = lib().hx_create_ex(device, dtype, metric, dim, int(capacity), CREATE_SCAN_ONLY if scan_only else 0, C.byref(h))
         if rc:
             raise HxError(rc, lib().hx_last_error(None).decode())
         self.h = h
@@ -245,6 +253,20 @@ class Engine:
     def set_queries_device(self, dev_ptr, n, normalize=False):
         self._ck(lib().hx_set_queries_device(self.h, C.c_void_p(dev_ptr), n, int(normalize)))
         self._nq = n
+
+    def append_halfvec_from(self, src, first=0, n=None):
+        """hx_append_rows_halfvec: appends `embedding::halfvec` of src's rows [first, first + n) (src: an F32 engine, self: F16), device to
+        device, f32_to_half bit for bit.  Raises HxError E_RANGE (self unchanged) when a finite element does not fit a half."""
+        n = src.num_rows - first if n is None else n
+        out = C.c_uint64()
+        self._ck(lib().hx_append_rows_halfvec(self.h, src.h, first, n, C.byref(out)))
+        return out.value
+
+    def set_queries_halfvec_from(self, src, normalize=False):
+        """hx_set_queries_halfvec: self's query slots become the halfvec casts of all of src's uploaded query slots."""
+        self._ck(lib().hx_set_queries_halfvec(self.h, src.h, int(normalize)))
+        self._nq = src._nq
+        return self._nq
 
     def distances(self, query, row_ids):
         q, _ = self._rows(query)
@@ -317,6 +339,24 @@ class Engine:
         dist = np.empty((nq, k), np.float64)
         cnt = np.empty(nq, np.uint32)
         self._ck(lib().hx_exact_search(self.h, op, first_query, nq, first_row, n_rows, _p(words), k, _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
+
+    def exact_rerank(self, op, candidates, k, first_query=0):
+        """hx_exact_rerank: per query slot first_query + i, the k rows of its candidate list nearest under the SQL operator `op` (OP_*), with
+        exactly exact_search's values, order and padding.  candidates: a tuple (offsets, ids) in CSR form (offsets: nq + 1 entries from 0), or
+        a list of per-query id arrays.  Returns (ids uint32[nq, k], dist float64[nq, k], counts uint32[nq])."""
+        if isinstance(candidates, tuple):
+            off, cand = np.ascontiguousarray(candidates[0], np.uint64), _u32(candidates[1])
+        else:
+            lists = [np.asarray(c, np.uint32).ravel() for c in candidates]
+            off = np.zeros(len(lists) + 1, np.uint64)
+            off[1:] = np.cumsum([len(c) for c in lists], dtype=np.uint64)
+            cand = _u32(np.concatenate(lists) if lists else np.empty(0, np.uint32))
+        nq = len(off) - 1
+        ids = np.empty((nq, k), np.uint32)
+        dist = np.empty((nq, k), np.float64)
+        cnt = np.empty(nq, np.uint32)
+        self._ck(lib().hx_exact_rerank(self.h, op, first_query, nq, _p(off), _p(cand), k, _p(ids), _p(dist), _p(cnt)))
         return ids, dist, cnt
 
     def exact_range(self, op, radius, cmp=CMP_LT, first_query=0, nq=None, first_row=0, n_rows=None, row_pass=None, packed=False,

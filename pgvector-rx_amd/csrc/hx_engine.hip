@@ -19,6 +19,8 @@
 // There is no CPU fallback anywhere in this file: without a GPU hx_create fails with HX_E_NODEVICE.
 #include "hx_ops.h"
 
+#include <charconv>
+
 static thread_local std::string g_create_err;
 
 // =================================================================================================
@@ -171,37 +173,6 @@ k_pair_groups(const uint8_t *__restrict__ rows, uint32_t pitch,
 // normalisation (a4): f64 norm accumulated in index order by ONE thread per row, exactly as
 // l2_normalize_raw (vector.rs:106-126): v*v is exact in f64 for f32-origin v, the sum is sequential.
 // =================================================================================================
-__device__ __forceinline__ unsigned short f32_to_half_ref(float f)
-{   // f32_to_half, halfvec.rs:92-143, INCLUDING its flush of |x| < 2^-24 to zero
-    unsigned int bits = __builtin_bit_cast(unsigned int, f);
-    unsigned int sign = (bits >> 31) & 1u;
-    int exp = (int)((bits >> 23) & 0xffu);
-    unsigned int mant = bits & 0x7fffffu;
-    if (exp == 0xff) {
-        if (mant == 0) return (unsigned short)((sign << 15) | (0x1fu << 10));
-        unsigned int m = mant >> 13; if (m < 1) m = 1;
-        return (unsigned short)((sign << 15) | (0x1fu << 10) | m);
-    }
-    if (exp > 142) return (unsigned short)((sign << 15) | (0x1fu << 10));
-    if (exp < 103) return (unsigned short)(sign << 15);
-    if (exp < 113) {
-        int shift = 113 - exp;
-        unsigned int full = mant | 0x800000u;
-        unsigned int m = full >> (shift + 13);
-        unsigned int round_bit = (full >> (shift + 12)) & 1u;
-        bool sticky = (full & ((1u << (shift + 12)) - 1u)) != 0;
-        unsigned int r = (sign << 15) | m;
-        if (round_bit && (sticky || (m & 1u))) r += 1;
-        return (unsigned short)r;
-    }
-    unsigned int half_exp = (unsigned int)(exp - 127 + 15) & 0x1fu;
-    unsigned int half_mant = mant >> 13;
-    unsigned int round_bit = (mant >> 12) & 1u, sticky = mant & 0xfffu;
-    unsigned int r = (sign << 15) | (half_exp << 10) | half_mant;
-    if (round_bit && (sticky || (half_mant & 1u))) r += 1;
-    return (unsigned short)r;
-}
-
 template <int DT>
 __global__ void k_normalize(uint8_t *rows, uint32_t pitch, int dim, uint64_t n, double *norms)
 {
@@ -236,6 +207,39 @@ __global__ void k_rows_equal(const uint8_t *__restrict__ rows, uint32_t pitch, u
     }
     unsigned long long diff = __ballot(!same);
     if (lane == 0) eq[p] = diff == 0ull;
+}
+
+// =================================================================================================
+// vector -> halfvec cast (vector_to_halfvec, halfvec.rs:644-670): f32_to_half_ref of every element, integer operations only.
+//   One thread per 16-byte fragment of a destination row (8 halves from 32 source bytes); elements past dim are written as
+//   zero (the row padding).  A finite element whose half is +-inf is the reference's range error (`rt.is_infinite() &&
+//   !val.is_infinite()`): the thread's first offending flat index (row * dim + element) goes to *bad by a global atomic min.
+//   HBM-bound: 6 B per element.
+// =================================================================================================
+__global__ void __launch_bounds__(256)
+k_cast_f16(const uint8_t *__restrict__ src, uint32_t src_pitch, uint8_t *__restrict__ dst, uint32_t dst_pitch, uint32_t dim,
+           uint32_t fpr, uint32_t n_frags, uint64_t row0, unsigned long long *__restrict__ bad)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_frags) return;
+    const uint32_t rl = t / fpr, f = t - rl * fpr, e0 = f * 8u;
+    const uint64_t r = row0 + rl;
+    const uint8_t *s = src + r * src_pitch + (size_t)e0 * 4u;
+    const u4 lo = *(const u4 *)s;                                  // e0 < dim: inside the source row
+    u4 hi = {0u, 0u, 0u, 0u};
+    if (e0 + 4u < dim) hi = *(const u4 *)(s + 16);
+    const unsigned int w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    unsigned int h[8];
+    uint32_t first_bad = 8;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const bool live = e0 + i < dim;
+        h[i] = live ? f32_to_half_ref(bits2f(w[i])) : 0u;
+        if (live && first_bad == 8 && (h[i] & 0x7fffu) == 0x7c00u && (w[i] & 0x7fffffffu) != 0x7f800000u) first_bad = i;
+    }
+    const u4 o = {h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+    *(u4 *)(dst + (uint64_t)rl * dst_pitch + (size_t)f * 16u) = o;
+    if (first_bad < 8) atomicMin(bad, (unsigned long long)(r * dim + e0 + first_bad));
 }
 
 // =================================================================================================
@@ -423,24 +427,34 @@ static int create_fail(int code, const std::string &msg) { g_create_err = msg; r
 
 int hx_create(int device, int dtype, int metric, int dim, uint64_t capacity_rows, hx_engine **out)
 {
+    return hx_create_ex(device, dtype, metric, dim, capacity_rows, 0, out);
+}
+
+int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_rows, int flags, hx_engine **out)
+{
     if (!out) return create_fail(HX_E_ARG, "out is NULL");
     *out = nullptr;
+    if (flags & ~HX_CREATE_SCAN_ONLY) return create_fail(HX_E_ARG, "unknown hx_create_ex flags");
+    const bool scan_only = (flags & HX_CREATE_SCAN_ONLY) != 0;
     if (dtype < HX_F32 || dtype > HX_SPARSE) return create_fail(HX_E_ARG, "unknown dtype");
     const bool bit_metric = metric == HX_HAMMING || metric == HX_JACCARD;
     if (metric < HX_L2SQ || metric > HX_JACCARD || bit_metric != (dtype == HX_BIT))
         return create_fail(HX_E_ARG, "metric does not belong to this dtype's operator classes");
     // index dimension limits: hnsw_constants.rs:4 (vector 2000), halfvec.rs:876 (2x), bitvec.rs:184 (32x); sparsevec: SPARSEVEC_MAX_DIM 1e9,
     // at most 1000 non-zero elements in an indexed value
-    const int max_dim = dtype == HX_F32 ? 2000 : dtype == HX_F16 ? 4000 : dtype == HX_BIT ? 64000 : 1000000000;
+    // scan-only engines (no index): the types' own limits, VECTOR_MAX_DIM vector.rs:30 and HALFVEC_MAX_DIM halfvec.rs:28
+    const bool type_limit = scan_only && (dtype == HX_F32 || dtype == HX_F16);
+    const int max_dim = type_limit ? 16000 : dtype == HX_F32 ? 2000 : dtype == HX_F16 ? 4000 : dtype == HX_BIT ? 64000 : 1000000000;
     if (dim < 1) return create_fail(HX_E_DIM, "column must have at least 1 dimension");
-    if (dim > max_dim) return create_fail(HX_E_DIM, "column cannot have more than " + std::to_string(max_dim) + " dimensions for hnsw index");
+    if (dim > max_dim) return create_fail(HX_E_DIM, type_limit ? std::string(dtype == HX_F32 ? "vector" : "halfvec") + " cannot have more than 16000 dimensions"
+                                                               : "column cannot have more than " + std::to_string(max_dim) + " dimensions for hnsw index");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return create_fail(HX_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
     if (device < 0 || device >= ndev) return create_fail(HX_E_ARG, "device index out of range");
     hx_engine *e = new (std::nothrow) hx_engine();
     if (!e) return create_fail(HX_E_NOMEM, "out of host memory");
-    e->device = device; e->dtype = dtype; e->metric = metric; e->dim = dim;
+    e->device = device; e->dtype = dtype; e->metric = metric; e->dim = dim; e->scan_only = scan_only;
     e->row_bytes = dtype == HX_F32 ? (uint64_t)dim * 4 : dtype == HX_F16 ? (uint64_t)dim * 2 : dtype == HX_BIT ? (uint64_t)(dim + 7) / 8
                  : (16 + 8 * (uint64_t)std::min(dim, HX_SPARSE_MAX_NNZ) + 15) & ~(uint64_t)15;      // sparsevec record (include/hnswrx.h)
     e->pitch = (e->row_bytes + 15) & ~(uint64_t)15;
@@ -475,7 +489,7 @@ int hx_destroy(hx_engine *e)
     HxMirror &mr = e->mirror;
     void *hp[] = {c.h_req, c.h_res, mr.h_stage, mr.io.h_io, mr.h_lk, e->grp.h_ctr, e->grp.h, e->bw.h, e->bw.h_ctr};
     void *dp[] = {c.d_req, c.d_res, e->d_rows, e->d_queries, mr.d_l0_ids, mr.d_l0_d, mr.d_l0_cnt, mr.d_level, mr.d_up_block, mr.d_up_ids, mr.d_up_d, mr.d_up_cnt, mr.io.d_vis, mr.d_stage, mr.io.d_io, mr.d_lk, mr.d_pm, mr.d_pm_valid, mr.io.d_spill,
-                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact, e->d_range};
+                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact, e->d_range, e->d_rerank};
     for (void *p : hp) if (p) (void)hipHostFree(p);
     for (void *p : dp) if (p) (void)hipFree(p);
     for (HxFusedIo &io : e->scan_io) {                           // pipelined scan slots: a launch still in flight is drained first
@@ -598,6 +612,108 @@ static int set_queries_impl(hx_engine *e, const void *q, uint32_t nq, int normal
 int hx_set_queries(hx_engine *e, const void *queries_host, uint32_t nq, int normalize) { return set_queries_impl(e, queries_host, nq, normalize, hipMemcpyHostToDevice); }
 int hx_set_queries_device(hx_engine *e, const void *queries_dev, uint32_t nq, int normalize) { return set_queries_impl(e, queries_dev, nq, normalize, hipMemcpyDeviceToDevice); }
 
+// ---- vector -> halfvec casts, device to device ---------------------------------------------------------------------------------------------
+static int cast_check(hx_engine *dst, const hx_engine *src)
+{
+    if (!dst) return HX_E_ARG;
+    if (!src) return dst->fail(HX_E_ARG, "source engine is NULL");
+    if (src->dtype != HX_F32 || dst->dtype != HX_F16) return dst->fail(HX_E_ARG, "the cast reads a vector (HX_F32) engine into a halfvec (HX_F16) engine");
+    if (src->device != dst->device) return dst->fail(HX_E_ARG, "source and destination engines are on different devices");
+    if (src->dim != dst->dim) return dst->fail(HX_E_DIM, "expected " + std::to_string(dst->dim) + " dimensions, not " + std::to_string(src->dim));
+    for (const HxFusedIo &io : dst->scan_io)
+        if (io.busy) return dst->fail(HX_E_STATE, "a pipelined index scan on the destination engine is in flight (hx_index_search_wait first)");
+    return HX_OK;
+}
+
+// casts n rows of `src` (pitch src_pitch) into `out` (dst's pitch) on dst's stream; *bad_out = first offending flat index, or ~0
+static int cast_run(hx_engine *dst, const uint8_t *src, uint64_t src_pitch, uint8_t *out, uint64_t n, unsigned long long *bad_out)
+{
+    *bad_out = ~0ull;
+    if (!n) return HX_OK;
+    unsigned long long *d_bad = nullptr;
+    HX_HIP(dst, hipMalloc((void **)&d_bad, sizeof(unsigned long long)));
+    const uint32_t fpr = (uint32_t)(dst->pitch / 16);
+    const uint64_t rows_per = std::max<uint64_t>(1, (1ull << 31) / fpr);      // 32-bit fragment index per launch
+    hipError_t s = hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), dst->stream);
+    if (s == hipSuccess && dst->timing) s = hipEventRecord(dst->ev0, dst->stream);
+    uint64_t launches = 0;
+    for (uint64_t r0 = 0; s == hipSuccess && r0 < n; r0 += rows_per) {
+        const uint32_t nf = (uint32_t)(std::min(rows_per, n - r0) * fpr);
+        hipLaunchKernelGGL(k_cast_f16, dim3((nf + 255) / 256), dim3(256), 0, dst->stream, src, (uint32_t)src_pitch, out + r0 * dst->pitch,
+                           (uint32_t)dst->pitch, (uint32_t)dst->dim, fpr, nf, r0, d_bad);
+        s = hipGetLastError();
+        launches++;
+    }
+    if (s == hipSuccess && dst->timing) s = hipEventRecord(dst->ev1, dst->stream);
+    if (s == hipSuccess) s = hipMemcpyAsync(bad_out, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, dst->stream);
+    if (s == hipSuccess) s = hipStreamSynchronize(dst->stream);
+    (void)hipFree(d_bad);
+    if (s != hipSuccess) return dst->fail(HX_E_HIP, std::string("vector -> halfvec cast: ") + hipGetErrorString(s));
+    if (dst->timing) {
+        float ms = 0.f;
+        HX_HIP(dst, hipEventElapsedTime(&ms, dst->ev0, dst->ev1));
+        dst->last_ms = ms; dst->stat_cast.launches += launches; dst->stat_cast.units += n * (uint64_t)dst->dim; dst->stat_cast.ms += ms;
+    }
+    return HX_OK;
+}
+
+// the reference's error for the first offending element: "<v>" is out of range for type halfvec (halfvec.rs:665), v as Rust's Display prints it
+static int cast_range_fail(hx_engine *dst, const uint8_t *src, uint64_t src_pitch, unsigned long long bad, const char *what, uint64_t first)
+{
+    const uint64_t r = bad / (uint64_t)dst->dim, i = bad % (uint64_t)dst->dim;
+    float v = 0.f;
+    HX_HIP(dst, hipMemcpy(&v, src + r * src_pitch + i * 4, 4, hipMemcpyDeviceToHost));
+    char buf[64];
+    const auto res = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::fixed);   // shortest round-trip digits, no exponent
+    return dst->fail(HX_E_RANGE, "\"" + std::string(buf, res.ptr) + "\" is out of range for type halfvec (" + what + " " + std::to_string(first + r) +
+                                 ", element " + std::to_string(i) + ")");
+}
+
+int hx_append_rows_halfvec(hx_engine *dst, const hx_engine *src, uint64_t first, uint64_t n, uint64_t *first_row_id)
+{
+    int rc = cast_check(dst, src);
+    if (rc) return rc;
+    if (first > src->n_rows || n > src->n_rows - first) return dst->fail(HX_E_ARG, "source row range out of bounds");
+    if (dst->n_rows + n > dst->capacity) return dst->fail(HX_E_NOMEM, "row store capacity exceeded (hx_create capacity_rows)");
+    if (dst->n_rows + n > 0x7fffffffull) return dst->fail(HX_E_NOMEM, "row ids are 31-bit");
+    HX_HIP(dst, hipSetDevice(dst->device));
+    const uint8_t *s = src->d_rows + first * src->pitch;
+    unsigned long long bad;
+    if ((rc = cast_run(dst, s, src->pitch, dst->d_rows + dst->n_rows * dst->pitch, n, &bad))) return rc;
+    if (bad != ~0ull) return cast_range_fail(dst, s, src->pitch, bad, "source row", first);   // written past n_rows only: nothing is committed
+    if (first_row_id) *first_row_id = dst->n_rows;
+    dst->n_rows += n;
+    return HX_OK;
+}
+
+int hx_set_queries_halfvec(hx_engine *dst, const hx_engine *src, int normalize)
+{
+    int rc = cast_check(dst, src);
+    if (rc) return rc;
+    const uint32_t nq = src->n_queries;
+    HX_HIP(dst, hipSetDevice(dst->device));
+    // the casts go to a buffer of their own (nq + 1 slots: it becomes the query store when that is too small; the last slot is hx_distances'),
+    // so that a range error leaves the uploaded queries as they were
+    uint8_t *buf = nullptr;
+    HX_HIP(dst, hipMalloc((void **)&buf, (size_t)(nq + 1) * dst->pitch));
+    unsigned long long bad;
+    rc = cast_run(dst, src->d_queries, src->pitch, buf, nq, &bad);
+    if (!rc && bad != ~0ull) rc = cast_range_fail(dst, src->d_queries, src->pitch, bad, "source query slot", 0);
+    if (!rc && nq > dst->cap_queries) {
+        std::swap(buf, dst->d_queries);
+        dst->cap_queries = nq;
+    } else if (!rc && nq) {
+        hipError_t s = hipMemcpyAsync(dst->d_queries, buf, (size_t)nq * dst->pitch, hipMemcpyDeviceToDevice, dst->stream);
+        if (s == hipSuccess) s = hipStreamSynchronize(dst->stream);
+        if (s != hipSuccess) rc = dst->fail(HX_E_HIP, std::string("hx_set_queries_halfvec: ") + hipGetErrorString(s));
+    }
+    (void)hipFree(buf);
+    if (rc) return rc;
+    dst->n_queries = nq;
+    if (normalize) return normalize_region(dst, dst->d_queries, nq, nullptr);
+    return HX_OK;
+}
+
 static int check_ids(hx_engine *e, const uint32_t *ids, size_t n)
 {
     for (size_t i = 0; i < n; i++)
@@ -605,10 +721,15 @@ static int check_ids(hx_engine *e, const uint32_t *ids, size_t n)
     return HX_OK;
 }
 
-int hx_distances_batch(hx_engine *e, uint32_t n_groups, const uint32_t *group_query,
-                       const uint32_t *group_offsets, const uint32_t *row_ids, float *out)
+// a scan-only engine (HX_CREATE_SCAN_ONLY) serves the row store, hx_distances and the exact scans; the lock-step batch and pair entries refuse it
+static int refuse_scan_only(hx_engine *e, const char *what)
 {
-    if (!e) return HX_E_ARG;
+    return e->fail(HX_E_STATE, std::string(what) + " is not available on a scan-only engine (HX_CREATE_SCAN_ONLY)");
+}
+
+static int distances_batch_impl(hx_engine *e, uint32_t n_groups, const uint32_t *group_query,
+                                const uint32_t *group_offsets, const uint32_t *row_ids, float *out)
+{
     if (n_groups == 0) return HX_OK;
     if (!group_query || !group_offsets || !row_ids || !out) return e->fail(HX_E_ARG, "NULL argument");
     const uint32_t n_ids = group_offsets[n_groups];
@@ -631,6 +752,14 @@ int hx_distances_batch(hx_engine *e, uint32_t n_groups, const uint32_t *group_qu
     return HX_OK;
 }
 
+int hx_distances_batch(hx_engine *e, uint32_t n_groups, const uint32_t *group_query,
+                       const uint32_t *group_offsets, const uint32_t *row_ids, float *out)
+{
+    if (!e) return HX_E_ARG;
+    if (e->scan_only) return refuse_scan_only(e, "hx_distances_batch");
+    return distances_batch_impl(e, n_groups, group_query, group_offsets, row_ids, out);
+}
+
 int hx_distances(hx_engine *e, const void *query_host, const uint32_t *row_ids, uint32_t n, float *out)
 {
     if (!e) return HX_E_ARG;
@@ -645,7 +774,7 @@ int hx_distances(hx_engine *e, const void *query_host, const uint32_t *row_ids, 
     const uint32_t G = 256, n_groups = (n + G - 1) / G;
     std::vector<uint32_t> gq(n_groups, HX_QUERY_SLOT | e->cap_queries), go(n_groups + 1);
     for (uint32_t g = 0; g <= n_groups; g++) go[g] = std::min(n, g * G);
-    return hx_distances_batch(e, n_groups, gq.data(), go.data(), row_ids, out);
+    return distances_batch_impl(e, n_groups, gq.data(), go.data(), row_ids, out);
 }
 
 int hx_pairwise_many(hx_engine *e, uint32_t n_groups, const uint32_t *group_offsets,
@@ -653,6 +782,7 @@ int hx_pairwise_many(hx_engine *e, uint32_t n_groups, const uint32_t *group_offs
                      const uint64_t *out_offsets, float *out)
 {
     if (!e) return HX_E_ARG;
+    if (e->scan_only) return refuse_scan_only(e, "hx_pairwise_many");
     if (n_groups == 0) return HX_OK;
     if (!group_offsets || !na || !nb || !ids || !out_offsets || !out) return e->fail(HX_E_ARG, "NULL argument");
     const uint32_t n_ids = group_offsets[n_groups];
@@ -684,6 +814,7 @@ int hx_pairwise_many_mfma(hx_engine *e, uint32_t n_groups, const uint32_t *group
                           const uint64_t *out_offsets, float *out, float *norm2_out)
 {
     if (!e) return HX_E_ARG;
+    if (e->scan_only) return refuse_scan_only(e, "hx_pairwise_many_mfma");
     if (n_groups == 0) return HX_OK;
     if (!group_offsets || !na || !nb || !ids || !out_offsets || !out) return e->fail(HX_E_ARG, "NULL argument");
     if (e->dtype != HX_F16 || e->metric != HX_NEG_IP) return e->fail(HX_E_ARG, "the MFMA pair path serves halfvec inner product");
@@ -718,6 +849,7 @@ int hx_pairwise_many_mfma(hx_engine *e, uint32_t n_groups, const uint32_t *group
 int hx_pairwise(hx_engine *e, const uint32_t *ids, uint32_t w, float *out)
 {
     if (!e) return HX_E_ARG;
+    if (e->scan_only) return refuse_scan_only(e, "hx_pairwise");
     if (w == 0) return HX_OK;
     if (!ids || !out) return e->fail(HX_E_ARG, "NULL argument");
     int rc;
@@ -773,6 +905,7 @@ int hx_pairwise(hx_engine *e, const uint32_t *ids, uint32_t w, float *out)
 int hx_rows_equal(hx_engine *e, uint32_t n_pairs, const uint32_t *a_ids, const uint32_t *b_ids, uint8_t *equal_out)
 {
     if (!e) return HX_E_ARG;
+    if (e->scan_only) return refuse_scan_only(e, "hx_rows_equal");
     if (n_pairs == 0) return HX_OK;
     if (!a_ids || !b_ids || !equal_out) return e->fail(HX_E_ARG, "NULL argument");
     int rc;
@@ -800,7 +933,7 @@ int hx_last_kernel_ms(hx_engine *e, float *ms) { if (!e || !ms) return HX_E_ARG;
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset)
 {
     if (!e) return HX_E_ARG;
-    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : kind == 8 ? e->stat_range : e->stat_mfma;
+    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : kind == 8 ? e->stat_range : kind == 9 ? e->stat_rerank : kind == 10 ? e->stat_cast : e->stat_mfma;
     if (kind == 5 && reset) { e->scan_epoch_set = false; e->scan_last_end = 0.0; }
     if (launches) *launches = s.launches;
     if (units) *units = s.units;

@@ -1,7 +1,8 @@
 // hx_exact.hip -- exact (filtered) k-NN scan on the device: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k`,
 // i.e. the executor calling the operator function on every heap row and keeping the top k (include/hnswrx.h: hx_exact_search).
 //
-// Values, the order key and the row streaming (ex_park / ex_eval) are those of hx_exact_core.h, shared with the range scans.
+// Values, the order key, the row streaming (ex_park / ex_eval) and the LDS sort (ex_sort / ex_keep) are those of hx_exact_core.h, shared
+// with the range scans and the re-rank.
 //
 // Order: ascending by the value under PostgreSQL's float8 comparison (-0.0 == +0.0, +inf < NaN, all NaNs equal), ties by ascending row id.
 // Each (value, id) is carried as the 64-bit order key (ex_key) and the id.
@@ -18,41 +19,6 @@
 namespace {
 
 constexpr int EX_MERGE_THREADS = 512;
-
-__device__ __forceinline__ bool ex_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
-
-// bitonic sort of P (a power of two) entries in LDS by (key, id), by the whole workgroup
-__device__ void ex_sort(uint64_t *key, uint32_t *id, uint32_t P)
-{
-    for (uint32_t k2 = 2; k2 <= P; k2 <<= 1)
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
-                const uint32_t x = i ^ j;
-                if (x > i) {
-                    const uint64_t ka = key[i], kb = key[x];
-                    const uint32_t ia = id[i], ib = id[x];
-                    if (ex_less(kb, ib, ka, ia) == ((i & k2) == 0)) { key[i] = kb; key[x] = ka; id[i] = ib; id[x] = ia; }
-                }
-            }
-            __syncthreads();
-        }
-}
-__device__ __forceinline__ uint32_t ex_pow2(uint32_t n) { uint32_t p = 2; while (p < n) p <<= 1; return p; }
-
-// sorts the n entries in skey/sid (LDS), keeps the best min(n, k); *cnt / *thr_k / *thr_i updated.  Whole workgroup, uniform arguments.
-__device__ void ex_keep(uint64_t *skey, uint32_t *sid, uint32_t n, uint32_t k, uint32_t *cnt, uint64_t *thr_k, uint32_t *thr_i)
-{
-    const uint32_t P = ex_pow2(n);
-    for (uint32_t i = n + threadIdx.x; i < P; i += blockDim.x) { skey[i] = ~0ull; sid[i] = ~0u; }
-    __syncthreads();
-    ex_sort(skey, sid, P);
-    if (threadIdx.x == 0) {
-        const uint32_t m = n < k ? n : k;
-        *cnt = m;
-        if (m == k) { *thr_k = skey[k - 1]; *thr_i = sid[k - 1]; }
-    }
-    __syncthreads();
-}
 
 // one query's candidate buffer in global scratch: sort through LDS, keep the k best
 __device__ void ex_prune(uint64_t *gkey, uint32_t *gid, uint32_t stride, uint64_t *skey, uint32_t *sid, uint32_t k, uint32_t *cnt, uint64_t *thr_k, uint32_t *thr_i)

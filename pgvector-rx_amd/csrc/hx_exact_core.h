@@ -38,6 +38,42 @@ __device__ __forceinline__ double ex_val(uint64_t key, bool neg_zero)
     return __builtin_bit_cast(double, (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key);
 }
 
+// top-k in LDS: entries ordered by (key, id); shared by the exact scan, its merge and the re-rank
+__device__ __forceinline__ bool ex_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
+// bitonic sort of P (a power of two) entries in LDS by (key, id), by the whole workgroup
+__device__ void ex_sort(uint64_t *key, uint32_t *id, uint32_t P)
+{
+    for (uint32_t k2 = 2; k2 <= P; k2 <<= 1)
+        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
+                const uint32_t x = i ^ j;
+                if (x > i) {
+                    const uint64_t ka = key[i], kb = key[x];
+                    const uint32_t ia = id[i], ib = id[x];
+                    if (ex_less(kb, ib, ka, ia) == ((i & k2) == 0)) { key[i] = kb; key[x] = ka; id[i] = ib; id[x] = ia; }
+                }
+            }
+            __syncthreads();
+        }
+}
+__device__ __forceinline__ uint32_t ex_pow2(uint32_t n) { uint32_t p = 2; while (p < n) p <<= 1; return p; }
+
+// sorts the n entries in skey/sid (LDS), keeps the best min(n, k); *cnt / *thr_k / *thr_i updated.  Whole workgroup, uniform arguments.
+__device__ void ex_keep(uint64_t *skey, uint32_t *sid, uint32_t n, uint32_t k, uint32_t *cnt, uint64_t *thr_k, uint32_t *thr_i)
+{
+    const uint32_t P = ex_pow2(n);
+    for (uint32_t i = n + threadIdx.x; i < P; i += blockDim.x) { skey[i] = ~0ull; sid[i] = ~0u; }
+    __syncthreads();
+    ex_sort(skey, sid, P);
+    if (threadIdx.x == 0) {
+        const uint32_t m = n < k ? n : k;
+        *cnt = m;
+        if (m == k) { *thr_k = skey[k - 1]; *thr_i = sid[k - 1]; }
+    }
+    __syncthreads();
+}
+
 // the f64 operator value from the lane partials (all lanes of the row's LPR-lane group get it)
 template <class OP, int HOP, int LPR>
 __device__ __forceinline__ double ex_value(const typename OP::acc_t &acc, float na, float nb)

@@ -1054,6 +1054,7 @@ int hx_index_create(hx_engine *e, int m, int ef_construction, hx_index **out)
 {
     if (!e || !out) return HX_E_ARG;
     *out = nullptr;
+    if (e->scan_only) return e->fail(HX_E_STATE, "a scan-only engine (HX_CREATE_SCAN_ONLY) cannot hold an index");
     // options.rs:203-225 ranges; build.rs:865-867 ef_construction >= 2m
     if (m < 2 || m > 100) return e->fail(HX_E_ARG, "m must be between 2 and 100");
     if (ef_construction < 4 || ef_construction > 1000) return e->fail(HX_E_ARG, "ef_construction must be between 4 and 1000");

@@ -122,6 +122,8 @@ struct hx_engine {
     HxKernelStat stat_dist, stat_pair, stat_fused, stat_links, stat_mfma, stat_wsel;
     HxKernelStat stat_exact; uint8_t *d_exact = nullptr; size_t cap_exact = 0;   // exact scans (hx_exact.hip): kind 7 counters, device scratch
     HxKernelStat stat_range; uint8_t *d_range = nullptr; size_t cap_range = 0;   // range scans (hx_range.hip): kind 8 counters, device scratch
+    HxKernelStat stat_rerank; uint8_t *d_rerank = nullptr; size_t cap_rerank = 0;   // exact re-rank (hx_rerank.hip): kind 9 counters, device scratch
+    HxKernelStat stat_cast; bool scan_only = false;                               // kind 10: vector -> halfvec casts; HX_CREATE_SCAN_ONLY (no index, no pair kernels)
     // pipelined scans: launches overlap, so their busy time is the UNION of the launches' [start, end] intervals (HIP events of each slot's stream,
     // measured from ev_scan_epoch on the engine's stream); stat_scan.ms = that union
     HxKernelStat stat_scan; hipEvent_t ev_scan_epoch = nullptr; bool scan_epoch_set = false; double scan_last_end = 0.0;

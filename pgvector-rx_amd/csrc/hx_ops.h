@@ -19,6 +19,36 @@ __device__ __forceinline__ float half2f(unsigned int h16)
 {   // exact widening, subnormals included (half_to_f32, halfvec.rs:54-87)
     return (float)__builtin_bit_cast(_Float16, (unsigned short)h16);
 }
+__device__ __forceinline__ unsigned short f32_to_half_ref(float f)
+{   // f32_to_half, halfvec.rs:92-143, INCLUDING its flush of |x| < 2^-24 to zero
+    unsigned int bits = __builtin_bit_cast(unsigned int, f);
+    unsigned int sign = (bits >> 31) & 1u;
+    int exp = (int)((bits >> 23) & 0xffu);
+    unsigned int mant = bits & 0x7fffffu;
+    if (exp == 0xff) {
+        if (mant == 0) return (unsigned short)((sign << 15) | (0x1fu << 10));
+        unsigned int m = mant >> 13; if (m < 1) m = 1;
+        return (unsigned short)((sign << 15) | (0x1fu << 10) | m);
+    }
+    if (exp > 142) return (unsigned short)((sign << 15) | (0x1fu << 10));
+    if (exp < 103) return (unsigned short)(sign << 15);
+    if (exp < 113) {
+        int shift = 113 - exp;
+        unsigned int full = mant | 0x800000u;
+        unsigned int m = full >> (shift + 13);
+        unsigned int round_bit = (full >> (shift + 12)) & 1u;
+        bool sticky = (full & ((1u << (shift + 12)) - 1u)) != 0;
+        unsigned int r = (sign << 15) | m;
+        if (round_bit && (sticky || (m & 1u))) r += 1;
+        return (unsigned short)r;
+    }
+    unsigned int half_exp = (unsigned int)(exp - 127 + 15) & 0x1fu;
+    unsigned int half_mant = mant >> 13;
+    unsigned int round_bit = (mant >> 12) & 1u, sticky = mant & 0xfffu;
+    unsigned int r = (sign << 15) | (half_exp << 10) | half_mant;
+    if (round_bit && (sticky || (half_mant & 1u))) r += 1;
+    return (unsigned short)r;
+}
 
 // xor-butterfly exchange v[lane ^ OFF] without touching LDS: __shfl_xor compiles to ds_bpermute_b32 (an LDS-crossbar round
 // trip, ~100+ cycles each, six in a row per reduced value -- measured as half of a row batch's time in the traversal
