@@ -87,6 +87,10 @@ int hx_create(int device, int dtype, int metric, int dim, uint64_t capacity_rows
  *   legal dim; hx_index_create, hx_distances_batch, hx_pairwise*, hx_rows_equal return HX_E_STATE.  Argument checks run before any device
  *   is touched, as in hx_create. */
 #define HX_CREATE_SCAN_ONLY 1
+/* HX_CREATE_NO_SIDECAR: no 8-bit row sidecar.  By default an HX_F32 / HX_L2SQ engine of more than 128 dimensions that is not scan-only keeps, next to
+ *   every row, a copy of it quantised to 8 bits per element (al16(dim) + 16 bytes per row of capacity, 0.78 GB per 1M x vector(768)), which the
+ *   index searches use to skip loading rows that cannot enter the result set; results are the same with and without it. */
+#define HX_CREATE_NO_SIDECAR 4
 int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_rows, int flags, hx_engine **out);
 int hx_destroy(hx_engine *e);
 
@@ -105,6 +109,16 @@ int hx_append_rows_device(hx_engine *e, const void *rows_dev, uint64_t n, uint64
 int hx_pop_rows(hx_engine *e, uint64_t n);
 /* Copies rows back (tests / page serialiser). */
 int hx_read_rows(hx_engine *e, uint64_t first, uint64_t n, void *rows_host);
+
+/* The 8-bit row sidecar (HX_CREATE_NO_SIDECAR above).  Every entry point that writes rows keeps it in step with them.  All three
+ * return HX_E_STATE on an engine without one.
+ *   hx_sidecar_read: codes of rows [first, first + n) (dim bytes per row; either pointer may be NULL) and {lo, step, e_x} (3 floats per row):
+ *     x^_i = fmaf(step, code_i, lo), e_x >= ||x - x^||_2 (+inf: the row is never skipped).
+ *   hx_sidecar_stats: since the last reset, rows whose f32 row the index searches fetched, and rows the bound let them skip.
+ *   hx_sidecar_bounds: lb_host[i] = the lower bound the searches use of d(query, ids[i]) (query: a row id, or HX_QUERY_SLOT | slot). */
+int hx_sidecar_read(hx_engine *e, uint64_t first, uint64_t n, void *codes_host, float *meta_host);
+int hx_sidecar_stats(hx_engine *e, uint64_t *rows_fetched, uint64_t *rows_rejected, int reset);
+int hx_sidecar_bounds(hx_engine *e, uint32_t query, const uint32_t *ids, uint32_t n, float *lb_host);
 
 /* L2-normalises rows [first, first+n) in place with the reference's f64 procedure
  * (l2_normalize_raw vector.rs:106-126, halfvec.rs:204-233 incl. its f32->half rounding);

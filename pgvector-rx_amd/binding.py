@@ -15,6 +15,7 @@ RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap or
 E_NOMEM = -3
 E_RANGE = -7                                           # a value out of range for the target type (the halfvec casts)
 CREATE_SCAN_ONLY = 1                                   # hx_create_ex: no index; vector / halfvec up to 16000 dims
+CREATE_NO_SIDECAR = 4                                  # hx_create_ex: no 8-bit row sidecar (f32 L2 engines keep one by default)
 QUERY_SLOT = 0x80000000
 _NP = {F32: np.float32, F16: np.uint16, BIT: np.uint8, SPARSE: np.uint8}
 SPARSE_MAX_NNZ = 1000
@@ -76,6 +77,9 @@ def lib():
         "hx_append_rows_device": (i32, [vp, vp, u64, C.POINTER(u64)]),
         "hx_pop_rows": (i32, [vp, u64]),
         "hx_read_rows": (i32, [vp, u64, u64, vp]),
+        "hx_sidecar_read": (i32, [vp, u64, u64, vp, vp]),
+        "hx_sidecar_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), i32]),
+        "hx_sidecar_bounds": (i32, [vp, u32, vp, u32, vp]),
         "hx_normalize_rows": (i32, [vp, u64, u64, vp]),
         "hx_set_queries": (i32, [vp, vp, u32, i32]),
         "hx_set_queries_device": (i32, [vp, vp, u32, i32]),
@@ -187,12 +191,13 @@ def _row_words(row_pass, n_rows, packed):
 class Engine:
     """hx_engine: device row store + batched distance kernels (replaces graph::DistanceFn)."""
 
-    def __init__(self, dtype, metric, dim, capacity, device=0, scan_only=False):
+    def __init__(self, dtype, metric, dim, capacity, device=0, scan_only=False, sidecar=True):
         """scan_only: an engine for the scan plans and re-ranking (hx_create_ex HX_CREATE_SCAN_ONLY): vector / halfvec up to 16000 dims,
-        never indexed."""
+        never indexed.  sidecar=False: HX_CREATE_NO_SIDECAR (same results, no 8-bit row copy for the searches to skip rows with)."""
         self.dtype, self.metric, self.dim = dtype, metric, dim
         h = C.c_void_p()
-        rc = lib().hx_create_ex(device, dtype, metric, dim, int(capacity), CREATE_SCAN_ONLY if scan_only else 0, C.byref(h))
+        flags = (CREATE_SCAN_ONLY if scan_only else 0) | (0 if sidecar else CREATE_NO_SIDECAR)
+        rc = lib().hx_create_ex(device, dtype, metric, dim, int(capacity), flags, C.byref(h))
         if rc:
             raise HxError(rc, lib().hx_last_error(None).decode())
         self.h = h
@@ -237,6 +242,26 @@ class Engine:
     def read_rows(self, first, n):
         out = np.empty((n, self.row_bytes // np.dtype(_NP[self.dtype]).itemsize), _NP[self.dtype])
         self._ck(lib().hx_read_rows(self.h, first, n, _p(out)))
+        return out
+
+    def sidecar_read(self, first, n):
+        """(codes uint8 [n, dim], meta float32 [n, 3] = lo, step, e_x) of rows [first, first + n)"""
+        codes = np.empty((n, self.dim), np.uint8)
+        meta = np.empty((n, 3), np.float32)
+        self._ck(lib().hx_sidecar_read(self.h, first, n, _p(codes), _p(meta)))
+        return codes, meta
+
+    def sidecar_stats(self, reset=False):
+        """(f32 rows the index searches fetched, rows the sidecar bound let them skip) since the last reset"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(lib().hx_sidecar_stats(self.h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value
+
+    def sidecar_bounds(self, query, row_ids):
+        """the searches' lower bound of d(query, row) per row id (query: a row id, or QUERY_SLOT | slot)"""
+        ids = _u32(row_ids)
+        out = np.empty(len(ids), np.float32)
+        self._ck(lib().hx_sidecar_bounds(self.h, query, _p(ids), len(ids), _p(out)))
         return out
 
     def normalize_rows(self, first, n):

@@ -25,6 +25,7 @@ SOURCES = {
     "hx_exact.hip": ["hx_ops.h", "hx_exact_core.h"],
     "hx_range.hip": ["hx_ops.h", "hx_exact_core.h"],
     "hx_rerank.hip": ["hx_ops.h", "hx_exact_core.h"],
+    "hx_sidecar.hip": ["hx_ops.h", "hx_fused_core.h"],
     "hx_group.hip": [],
     "hx_batch.hip": ["hx_ops.h"],
     "hx_index.cpp": [],

@@ -434,7 +434,7 @@ int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_r
 {
     if (!out) return create_fail(HX_E_ARG, "out is NULL");
     *out = nullptr;
-    if (flags & ~HX_CREATE_SCAN_ONLY) return create_fail(HX_E_ARG, "unknown hx_create_ex flags");
+    if (flags & ~(HX_CREATE_SCAN_ONLY | HX_CREATE_NO_SIDECAR)) return create_fail(HX_E_ARG, "unknown hx_create_ex flags");
     const bool scan_only = (flags & HX_CREATE_SCAN_ONLY) != 0;
     if (dtype < HX_F32 || dtype > HX_SPARSE) return create_fail(HX_E_ARG, "unknown dtype");
     const bool bit_metric = metric == HX_HAMMING || metric == HX_JACCARD;
@@ -471,6 +471,12 @@ int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_r
     CREATE_HIP(hipEventCreate(&e->ev5));
     s = hipMalloc((void **)&e->d_rows, e->capacity * e->pitch);
     if (s != hipSuccess) { hx_destroy(e); return create_fail(HX_E_NOMEM, "cannot reserve row store in HBM"); }
+    if (dtype == HX_F32 && metric == HX_L2SQ && !scan_only && !(flags & HX_CREATE_NO_SIDECAR) && e->pitch > 512) {   // the traversal's 64-lane rows (launch_fused_mode)
+        e->sc_pitch = (uint32_t)al16((size_t)dim);
+        s = hipMalloc((void **)&e->d_sc_codes, e->capacity * e->sc_pitch);
+        if (s == hipSuccess) s = hipMalloc((void **)&e->d_sc_meta, e->capacity * HX_SC_META * sizeof(float));
+        if (s != hipSuccess) { hx_destroy(e); return create_fail(HX_E_NOMEM, "cannot reserve the row sidecar in HBM (HX_CREATE_NO_SIDECAR goes without it)"); }
+    }
     e->cap_queries = 64;
     CREATE_HIP(hipMalloc((void **)&e->d_queries, (size_t)(e->cap_queries + 1) * e->pitch));
     CREATE_HIP(hipMemsetAsync(e->d_queries, 0, (size_t)(e->cap_queries + 1) * e->pitch, e->stream));
@@ -489,7 +495,7 @@ int hx_destroy(hx_engine *e)
     HxMirror &mr = e->mirror;
     void *hp[] = {c.h_req, c.h_res, mr.h_stage, mr.io.h_io, mr.h_lk, e->grp.h_ctr, e->grp.h, e->bw.h, e->bw.h_ctr};
     void *dp[] = {c.d_req, c.d_res, e->d_rows, e->d_queries, mr.d_l0_ids, mr.d_l0_d, mr.d_l0_cnt, mr.d_level, mr.d_up_block, mr.d_up_ids, mr.d_up_d, mr.d_up_cnt, mr.io.d_vis, mr.d_stage, mr.io.d_io, mr.d_lk, mr.d_pm, mr.d_pm_valid, mr.io.d_spill,
-                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact, e->d_range, e->d_rerank};
+                  mr.d_disc, mr.d_emask, mr.d_spill_big, mr.d_vis_big, e->grp.d, e->bw.d, e->bw.d_rec, e->d_xl, e->bw.d_wtab, e->bw.d_wt_valid, e->d_mf_norm2, e->d_wg, e->wsel.d_wl, e->wsel.d_cnt, e->wsel.d_slot, e->wsel.d_task, e->wsel.d_layer, e->wsel.d_counters, e->d_exact, e->d_range, e->d_rerank, e->d_sc_codes, e->d_sc_meta};
     for (void *p : hp) if (p) (void)hipHostFree(p);
     for (void *p : dp) if (p) (void)hipFree(p);
     for (HxFusedIo &io : e->scan_io) {                           // pipelined scan slots: a launch still in flight is drained first
@@ -534,6 +540,8 @@ static int append_impl(hx_engine *e, const void *rows, uint64_t n, uint64_t *fir
         if (kind == hipMemcpyDeviceToDevice) HX_HIP(e, hipDeviceSynchronize());
         if (e->pitch != e->row_bytes) HX_HIP(e, hipMemsetAsync(dst, 0, n * e->pitch, e->stream));
         HX_HIP(e, hipMemcpy2DAsync(dst, e->pitch, rows, e->row_bytes, e->row_bytes, n, kind, e->stream));
+        int rc;
+        if ((rc = hx_sidecar_encode(e, e->n_rows, n))) return rc;
         HX_HIP(e, hipStreamSynchronize(e->stream));
     }
     if (first) *first = e->n_rows;
@@ -585,7 +593,11 @@ int hx_normalize_rows(hx_engine *e, uint64_t first, uint64_t n, double *norms_ho
     if (!e) return HX_E_ARG;
     if (first + n > e->n_rows) return e->fail(HX_E_ARG, "row range out of bounds");
     HX_HIP(e, hipSetDevice(e->device));
-    return normalize_region(e, e->d_rows + first * e->pitch, n, norms_host);
+    int rc;
+    if ((rc = normalize_region(e, e->d_rows + first * e->pitch, n, norms_host))) return rc;
+    if ((rc = hx_sidecar_encode(e, first, n))) return rc;
+    HX_HIP(e, hipStreamSynchronize(e->stream));
+    return HX_OK;
 }
 
 static int set_queries_impl(hx_engine *e, const void *q, uint32_t nq, int normalize, hipMemcpyKind kind)

@@ -310,6 +310,7 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
     p.spill = (uint2 *)spill_ptr; p.spill_stride = ccap;
     { const char *dv = getenv("HX_F_DBG"); p.fdbg = dv ? (uint32_t)atoi(dv) : 0u; }
     p.sa = sa ? 1u : 0u;
+    p.sc_codes = d_sc_codes; p.sc_meta = d_sc_meta; p.sc_pitch = sc_pitch; p.dim = (uint32_t)dim;
     p.vis = vis_ptr ? vis_ptr : io.d_vis; p.vis_words = vis_words;
     p.next_task = (uint32_t *)(io.d_io + o_ctr);
     p.n_dist = (unsigned long long *)(io.d_io + o_ctr + 8);
@@ -379,6 +380,7 @@ int hx_engine::fused_collect(HxFusedIo &io, uint32_t *out_ids, float *out_d, uin
                 mode, ntasks, nd[3], nd[4], nd[5], nd[6], nd[7], nd[8], nd[9], nd[10], nd[11], nd[12], nd[13], nd[14], nd[15], nd[16]);
     if (counts) { counts[0] = nd[0]; counts[1] = nd[1]; }
     if (nd[2] > fused_cmax) fused_cmax = nd[2];
+    { unsigned long long sc[2]; memcpy(sc, io.h_io + o_ctr + 8 + 17 * 8, 16); sc_rows += sc[0]; sc_rej += sc[1]; }
     if (io.timed) {
         float ms = 0.f; HX_HIP(this, hipEventElapsedTime(&ms, io.ev0, io.ev1));
         last_ms = ms; stat_fused.launches++; stat_fused.units += nd[0] + nd[1]; stat_fused.ms += ms;

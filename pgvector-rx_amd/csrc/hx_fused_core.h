@@ -32,6 +32,9 @@
 #ifndef FUSED_MINW_ITER
 #define FUSED_MINW_ITER 3          /* the iterative-scan kernel carries more state: 168 VGPRs instead of spilling 230 */
 #endif
+#ifndef HX_SC_PASSES
+#define HX_SC_PASSES 2         /* sidecar bound: 4-row passes per round of code loads (f_lb_reject): 8 rows per memory hop; 4 spill 46 VGPRs in k_fused<query> */
+#endif
 #define FUSED_CG 3             /* ... times chunks of each requested at once */
 #define FUSED_CCAP 8192u       /* candidate-heap capacity per search (LDS head + global spill) */
 #define FUSED_MAXL 8           /* layers 0..7 handled on the device (P(level >= 8) = 16^-8 at m=16) */
@@ -70,6 +73,9 @@ struct FusedParams {
     uint32_t *out_tix;                            // which heap TID of the element each output is
     uint32_t sa;                                  // 1: searches with ef > 1 run on one sorted array (f_search_layer_sa); ties are redone by the heap kernel
     uint32_t fdbg;                                // experiments (HX_F_DBG): 1 no pre-filter, 4 phase timers into n_dist[3..7]
+    // 8-bit row sidecar (f32 L2, 64 lanes per row; nullptr: off): codes [n_rows][sc_pitch], {lo, step, e_x, 0} per row (hx_ops.h).
+    // n_dist[17] = f32 rows fetched by the searches, n_dist[18] = rows the bound rejected before their f32 row was fetched
+    const uint8_t *sc_codes; const float *sc_meta; uint32_t sc_pitch, dim;
 };
 
 // The traversal kernels read their parameter block IN PLACE from the kernarg segment (constant address space: scalar loads), through a
@@ -332,6 +338,7 @@ struct FusedCtx {
     const uint8_t *skip; uint32_t skip_self;                                        // MODE 3 repair searches (nullptr: no skip set)
     GStore DS; lds_uint2 *DP, *WS; uint32_t *LV; uint32_t dlen, vcount;           // iterative scan: `discarded` min-heap, visited ids so far (the set survives resumes)
     unsigned long long nd0, nd1; uint32_t cmax;
+    uint32_t nrow, nrej;                                                          // sidecar searches: f32 rows fetched, rows the bound rejected
     uint32_t tph[14];  // [13] select phase; diagnostic phase clocks (HX_F_DBG & 4): pop, list fetch, visited, compaction, distances, settle+prefilter, replay; [7] expansions, [8] heap pushes
 };
 
@@ -505,6 +512,85 @@ __device__ __forceinline__ float f_dist_batch(const FRows &p, const lds_u8 *qv, 
     return mine;
 #undef FD_TICK
     }
+}
+
+// The sidecar bound (hx_ops.h: hx_l2_lb_finish) of rows ids[0..n) against the f32 query parked at qv; returns a wave-uniform mask whose bit j is set
+// when 0 < LB(q, ids[j]) and LB >= thr, i.e. when the row's canonical distance is >= thr as well (LB = 0 never rejects: rows with a NaN distance, f = 0).
+// 16 lanes per row (16 codes = one 16-byte load per lane and 256-byte chunk), 4 rows per load instruction, HX_SC_PASSES such instructions x FUSED_CG
+// chunks in flight per round: with 2 passes, 8 rows of a 768-dim list are one memory hop, and a list of n new rows takes ceil(n / 8) dependent hops
+// before its f32 loads start (4 passes would make it one hop for 16 rows, but spill 46 VGPRs in k_fused<query>).  Row bases are per 16-lane group;
+// lanes past the batch re-read its first row.  A lane's query fragment is read from LDS once for the P rows.  D^ is summed per lane and then over the
+// 16 lanes: an order the bound allows.
+struct FCodes { const uint8_t *codes; const float *meta; uint32_t cpitch, dim, nterm; };
+// WRITE (hx_sidecar_bounds, tests): out[j] = LB(q, ids[j]) instead of the mask
+template <bool WRITE = false>
+__device__ __forceinline__ unsigned long long f_lb_reject(const FCodes &c, const lds_u8 *qv, const uint32_t *ids, uint32_t n, uint32_t lane, float thr, float *out = nullptr)
+{
+    constexpr int P = HX_SC_PASSES;
+    const uint32_t g = lane >> 4, l16 = lane & 15u;
+    const uint32_t nck = (c.cpitch + 255u) >> 8;
+    unsigned long long rej = 0ull;
+    for (uint32_t j0 = 0; j0 < n; j0 += 4u * P) {
+        const uint8_t *rb[P]; float lo[P], st[P], ex[P], acc[P];
+#pragma unroll
+        for (int s = 0; s < P; s++) {
+            const uint32_t j = j0 + 4u * (uint32_t)s + g;
+            const uint32_t id = ids[j < n ? j : j0];
+            rb[s] = c.codes + (size_t)id * c.cpitch;
+            const float4 m = *(const float4 *)(c.meta + (size_t)id * HX_SC_META);
+            lo[s] = m.x; st[s] = m.y; ex[s] = m.z; acc[s] = 0.0f;
+        }
+#pragma unroll 1
+        for (uint32_t c0 = 0; c0 < nck; c0 += FUSED_CG) {
+            const uint32_t kc = nck - c0 < (uint32_t)FUSED_CG ? nck - c0 : (uint32_t)FUSED_CG;
+            u4 rv[P][FUSED_CG]; uint32_t off[FUSED_CG];
+#pragma unroll
+            for (int k = 0; k < FUSED_CG; k++) { const uint32_t o = (c0 + (uint32_t)k) * 256u + l16 * 16u; off[k] = o < c.cpitch ? o : 0u; }
+            if (kc == (uint32_t)FUSED_CG) {
+#pragma unroll
+                for (int k = 0; k < FUSED_CG; k++)
+#pragma unroll
+                    for (int s = 0; s < P; s++) rv[s][k] = *(const u4 *)(rb[s] + off[k]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < FUSED_CG - 1; k++)
+                    if ((uint32_t)k < kc) {
+#pragma unroll
+                        for (int s = 0; s < P; s++) rv[s][k] = *(const u4 *)(rb[s] + off[k]);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < FUSED_CG; k++) {
+                const uint32_t i0 = (c0 + (uint32_t)k) * 256u + l16 * 16u;
+                if ((uint32_t)k < kc && i0 < c.dim) {
+                    const uint32_t lim = c.dim - i0;                  // >= 16 except in a row's last, partial chunk: its terms past dim are 0
+                    // one 16-byte query fragment (4 floats) at a time, for the P rows: few registers live next to the codes in flight
+#pragma unroll
+                    for (int w = 0; w < 4; w++) {
+                        const u4 qw = *(const lds_u4 *)(qv + 4u * i0 + 16u * (uint32_t)w);
+#pragma unroll
+                        for (int s = 0; s < P; s++) {
+#pragma unroll
+                            for (int t = 0; t < 4; t++) {
+                                const float xh = fmaf(st[s], (float)((rv[s][k][w] >> (8 * t)) & 0xffu), lo[s]);
+                                const float d = (uint32_t)(4 * w + t) < lim ? bits2f(qw[t]) - xh : 0.0f;
+                                acc[s] = fmaf(d, d, acc[s]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < P; s++) {
+            const float lb = hx_l2_lb_finish(lanes_sum_f<16>(acc[s]), ex[s], c.nterm);
+            if constexpr (WRITE) { if (l16 == 0u && j0 + 4u * (uint32_t)s + g < n) out[j0 + 4u * (uint32_t)s + g] = lb; continue; }
+            const unsigned long long b = __ballot(l16 == 0u && j0 + 4u * (uint32_t)s + g < n && lb > 0.0f && lb >= thr);   // LB 0 never rejects (NaN rows, f = 0)
+            const unsigned long long r4 = (b & 1ull) | ((b >> 15) & 2ull) | ((b >> 30) & 4ull) | ((b >> 45) & 8ull);   // lanes 0/16/32/48 -> rows +0..3
+            rej |= r4 << (j0 + 4u * (uint32_t)s);
+        }
+    }
+    return rej;
 }
 
 // check_element_closer (graph/mod.rs:315-339): is any d(q, ids[j]) <= thr?  Rows are evaluated FUSED_RB at a time in list

@@ -9,11 +9,13 @@
 // ITER: search_layer_disk WITH the iterative scan's state (scan.rs:302-448): the visited set is the caller's and survives
 // resumes (fresh == false keeps it; eps_visited == false: resume_scan_items' entry points are already in it), and every
 // visited element that does not end in W goes to the `discarded` min-heap, in the reference's order of pushes.
-template <class OP, int LPR, bool ITER = false, bool SKIP = false>
+// SC: the sidecar bound may skip rows (layer 0 of k_fused<query> only)
+template <class OP, int LPR, bool ITER = false, bool SKIP = false, bool SC = false>
 __device__ __forceinline__ void f_search_layer(KParams &p_in, FusedCtx &cx, uint32_t n_ep, uint32_t ef, int layer, bool scan, bool fresh = true, bool eps_visited = true)
 {
     KParams &p = f_params_here(p_in);
     const uint32_t lane = cx.lane;
+    constexpr bool kSidecar = SC && std::is_same<OP, OpF32<K_L2>>::value && LPR == 64 && !ITER;   // the 8-bit sidecar bound (hx_ops.h)
     // A greedy step (ef = 1) visits a few dozen ids: it uses the first 1 024 words of the table, so clearing costs 4 KB instead of 32-64 KB per
     // layer of the descent (the clears were 4 % of a query's memory traffic).  Any table size gives the same visited SET; one that fills up reports
     // FS_OVERFLOW and the task is retried with roomier tables, as for the full-size table.
@@ -203,15 +205,34 @@ __device__ __forceinline__ void f_search_layer(KParams &p_in, FusedCtx &cx, uint
             if (unvis) cx.IDS[__popcll(mask & ((1ull << lane) - 1ull))] = e;
             if constexpr (FUSED_BAR_BEFORE_ROWS) F_BAR(); else F_WSYNC();   // the ids are read back by this wave (LDS is in order); no wait for the visited-set CAS still in flight: it is settled after the row loads
             F_TICK(3);
-            const float mine = f_dist<OP, LPR>(cx, cx.QV, cx.IDS, cnt, lane, tm ? cx.tph : nullptr);
+            // nf: rows whose f32 row is fetched.  Where the pre-filter below is active, a row whose sidecar bound already reaches W's furthest
+            // distance f has d >= f and would be rejected by it: its f32 row is never loaded, and the survivors are compacted in list order, so the
+            // replay sees exactly the rows the pre-filter keeps, in the same order.  Not in ITER: `discarded` needs every distance.
+            uint32_t nf = cnt;
+            if constexpr (kSidecar) {
+                if (p.sc_codes && rlen >= ef && wl && !(p.fdbg & 1u)) {
+                    const float f0 = __builtin_bit_cast(float, (unsigned int)WA[0].x);
+                    const unsigned long long rej = f_lb_reject(FCodes{p.sc_codes, p.sc_meta, p.sc_pitch, p.dim, p.pitch >> 2}, cx.QV, cx.IDS, cnt, lane, f0);
+                    if (rej) {
+                        const unsigned long long sm = __ballot(lane < cnt) & ~rej;
+                        const uint32_t my = lane < cnt ? cx.IDS[lane] : 0u;
+                        F_WSYNC();
+                        if ((sm >> lane) & 1ull) cx.IDS[__popcll(sm & ((1ull << lane) - 1ull))] = my;
+                        F_WSYNC();
+                        nf = (uint32_t)__popcll(sm);
+                    }
+                }
+            }
+            const float mine = f_dist<OP, LPR>(cx, cx.QV, cx.IDS, nf, lane, tm ? cx.tph : nullptr);
             F_TICK(4);
             vis_settle(cx.vis, bmask, e, vslot, vold);                               // the CAS results came back with the rows
-            if (lane < cnt) cx.RES[lane] = fh_pack(mine, cx.IDS[lane]);
+            if (lane < nf) cx.RES[lane] = fh_pack(mine, cx.IDS[lane]);
             cx.nd0 += cnt;
+            if constexpr (kSidecar) { cx.nrow += nf; cx.nrej += cnt - nf; }
             // Pre-filter in parallel: once W is full (result_len >= ef) its furthest distance f only shrinks while this
             // list is replayed, so a row with d >= f NOW can never be added later in the replay; lane 0 then visits only the
             // survivors, in list order, and re-tests each against the current f -- same pushes, same order, as mod.rs:226-243.
-            bool keep = lane < cnt;
+            bool keep = lane < nf;
             if (keep && rlen >= ef && wl && !(p.fdbg & 1u)) {
                 const float f0 = __builtin_bit_cast(float, (unsigned int)WA[0].x);
                 keep = scan ? !((double)mine >= (double)f0) : (mine < f0);
@@ -467,7 +488,7 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
     cx.WH.lds = (lds_uint2 *)cx.W; cx.WH.glob = nullptr; cx.WH.L = 0xffffffffu;
     cx.lane = lane_in;
     cx.vis = p.vis + (size_t)slot * p.vis_words;
-    cx.nd0 = cx.nd1 = 0; cx.cmax = 0;
+    cx.nd0 = cx.nd1 = 0; cx.cmax = 0; cx.nrow = cx.nrej = 0;
     for (int i = 0; i < 14; i++) cx.tph[i] = 0;
     const uint32_t lane = cx.lane;
 
@@ -594,7 +615,7 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
                 } else
 #endif
                 {
-                f_search_layer<OP, LPR, false>(p, cx, n_ep, p.ef, 0, true);                  // scan.rs:515-528
+                f_search_layer<OP, LPR, false, false, true>(p, cx, n_ep, p.ef, 0, true);     // scan.rs:515-528
                 const uint32_t wl = cx.CTL[1];
                 f_sort_results(cx, wl, true);                                        // nearest LAST
                 cnt = wl < p.k ? wl : p.k;
@@ -707,6 +728,7 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
         F_BAR();
     }
     if (lane == 0) { atomicAdd(&p.n_dist[0], cx.nd0); atomicAdd(&p.n_dist[1], cx.nd1); atomicMax(&p.n_dist[2], (unsigned long long)cx.cmax);
+                     if (MODE == 0 && std::is_same<OP, OpF32<K_L2>>::value && LPR == 64 && p.sc_codes) { atomicAdd(&p.n_dist[17], cx.nrow); atomicAdd(&p.n_dist[18], cx.nrej); }
                      if (FUSED_TIMERS_ON && (p.fdbg & 4u)) { for (int i = 0; i < 14; i++) atomicAdd(&p.n_dist[3 + i], (unsigned long long)cx.tph[i]); } }
 }
 

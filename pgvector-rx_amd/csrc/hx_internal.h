@@ -124,6 +124,9 @@ struct hx_engine {
     HxKernelStat stat_range; uint8_t *d_range = nullptr; size_t cap_range = 0;   // range scans (hx_range.hip): kind 8 counters, device scratch
     HxKernelStat stat_rerank; uint8_t *d_rerank = nullptr; size_t cap_rerank = 0;   // exact re-rank (hx_rerank.hip): kind 9 counters, device scratch
     HxKernelStat stat_cast; bool scan_only = false;                               // kind 10: vector -> halfvec casts; HX_CREATE_SCAN_ONLY (no index, no pair kernels)
+    // 8-bit row sidecar (hx_sidecar.hip): f32 L2 engines with 64-lane rows, unless HX_CREATE_NO_SIDECAR.  codes [capacity][sc_pitch],
+    // {lo, step, e_x, 0} per row; sc_rows / sc_rej: f32 rows the traversal fetched / rows the bound rejected (hx_sidecar_stats)
+    uint8_t *d_sc_codes = nullptr; float *d_sc_meta = nullptr; uint32_t sc_pitch = 0; uint64_t sc_rows = 0, sc_rej = 0;
     // pipelined scans: launches overlap, so their busy time is the UNION of the launches' [start, end] intervals (HIP events of each slot's stream,
     // measured from ev_scan_epoch on the engine's stream); stat_scan.ms = that union
     HxKernelStat stat_scan; hipEvent_t ev_scan_epoch = nullptr; bool scan_epoch_set = false; double scan_last_end = 0.0;
@@ -199,6 +202,9 @@ struct hx_engine {
                   uint64_t counts[2], const HxFusedIter *it = nullptr, HxFusedView *view = nullptr, uint32_t roomy = 1, const HxFusedDev *dev = nullptr);   // roomy > 1: retry of overflowed tasks with that many times the visited table and candidate heap
     int fail(int code, const std::string &msg) { err = msg; return code; }
 };
+
+// hx_sidecar.hip: (re-)encodes the sidecar of rows [first, first + n) on the engine stream (no-op without a sidecar)
+int hx_sidecar_encode(hx_engine *e, uint64_t first, uint64_t n);
 
 // hx_sparse.hip: the sparsevec kernels (same request arrays as K1 / K2)
 #define HX_SPARSE_MAX_NNZ 1000

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
@@ -316,3 +317,26 @@ __device__ __forceinline__ void tri_decode(uint32_t p, uint32_t &i, uint32_t &j)
     } while (0)
 
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// ---- 8-bit row sidecar of f32 L2 engines (hx_sidecar.hip) ----------------------------------------------------------------
+// Row x (dim floats) is kept a second time as codes c_i (one byte each) and {lo, step, e_x}: x^_i = fmaf(step, c_i, lo) -- exactly this
+// expression, on the host and the device -- and e_x >= ||x - x^||_2 (computed in f64 from that same x^, rounded up; +inf where no bound is trusted).
+// hx_l2_lb_finish turns D^ = sum_i (q_i - x^_i)^2, evaluated in f32 in ANY order, into a lower bound of the canonical squared L2 distance
+// d(q, x) of f_dist_batch (n = terms of that sum, the row's f32 words):  LB = (1-g) * max(0, sqrt(D^ (1-g)) - e_x)^2, g = (n + 16) 2^-23.
+// Any inf / NaN, and any LB below 2^-100 (the underflow slack), gives 0.
+#define HX_SC_META 4            /* floats of row metadata: lo, step, e_x, 0 */
+__host__ __device__ __forceinline__ float hx_l2_lb_finish(float dhat, float ex, uint32_t n)
+{
+    const float g = 1.0f - (float)(n + 16u) * 0x1p-23f;                // exact: (2^23 - n - 16) 2^-23
+    const float t = sqrtf(dhat * g) - ex;
+    const float lb = g * (t * t);
+    if (!(t > 0.0f) || !(lb <= 3.402823466e+38f) || lb < 0x1p-100f) return 0.0f;
+    return lb;
+}
+// the same bound, D^ summed sequentially (tests/test_sidecar_bound_host.py; the kernels sum lane-parallel)
+__host__ __device__ inline float hx_l2_lb(const float *q, const uint8_t *codes, const float *meta, uint32_t dim, uint32_t n)
+{
+    float s = 0.0f;
+    for (uint32_t i = 0; i < dim; i++) { const float d = q[i] - fmaf(meta[1], (float)codes[i], meta[0]); s = fmaf(d, d, s); }
+    return hx_l2_lb_finish(s, meta[2], n);
+}
