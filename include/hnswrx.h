@@ -91,6 +91,11 @@ int hx_create(int device, int dtype, int metric, int dim, uint64_t capacity_rows
  *   every row, a copy of it quantised to 8 bits per element (al16(dim) + 16 bytes per row of capacity, 0.78 GB per 1M x vector(768)), which the
  *   index searches use to skip loading rows that cannot enter the result set; results are the same with and without it. */
 #define HX_CREATE_NO_SIDECAR 4
+/* HX_CREATE_SCAN_SIDECAR: a scan-only engine keeps no sidecar unless this flag asks for one.  Legal only together with HX_CREATE_SCAN_ONLY on an
+ *   HX_F32 / HX_L2SQ engine of more than 128 dimensions and without HX_CREATE_NO_SIDECAR (HX_E_ARG otherwise).  The engine then keeps and maintains
+ *   the sidecar exactly as a default engine does (al16(dim) + 16 bytes per row of capacity; hx_sidecar_read / _bounds work on it), and
+ *   hx_exact_search / hx_exact_range use it as described there: on vector(3072) a skipped row saves 12 KB. */
+#define HX_CREATE_SCAN_SIDECAR 8
 int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_rows, int flags, hx_engine **out);
 int hx_destroy(hx_engine *e);
 
@@ -119,6 +124,10 @@ int hx_read_rows(hx_engine *e, uint64_t first, uint64_t n, void *rows_host);
 int hx_sidecar_read(hx_engine *e, uint64_t first, uint64_t n, void *codes_host, float *meta_host);
 int hx_sidecar_stats(hx_engine *e, uint64_t *rows_fetched, uint64_t *rows_rejected, int reset);
 int hx_sidecar_bounds(hx_engine *e, uint32_t query, const uint32_t *ids, uint32_t n, float *lb_host);
+/* The exact scans' use of the sidecar: since the last reset, over the hx_exact_search / hx_exact_range calls that took the sidecar path (see there),
+ * code rows read (passing rows x query tiles) and f32 rows read.  Counted on the device.  An engine without a sidecar reports zeros; NULL engine:
+ * HX_E_ARG.  hx_sidecar_stats (the index searches' counters) is separate. */
+int hx_exact_sidecar_stats(hx_engine *e, uint64_t *rows_coded, uint64_t *rows_fetched, int reset);
 
 /* L2-normalises rows [first, first+n) in place with the reference's f64 procedure
  * (l2_normalize_raw vector.rs:106-126, halfvec.rs:204-233 incl. its f32->half rounding);
@@ -220,7 +229,13 @@ int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units,
  * past the uploaded slots, NULL outputs.  Synchronous on the engine stream; reads only, so it may run while a pipelined index scan
  * (hx_index_search_submit) is in flight.  The top-k scratch on the device is bounded independently of n_rows and nq (query blocks run in
  * turn; HX_EXACT_SCRATCH bytes, default 256 MiB); a filtered call also keeps its bitmap (n_rows / 8 B) and the list of passing row ids
- * (4 B each) there.  hx_kernel_stats kind 7 times the kernels only, not the bitmap upload. */
+ * (4 B each) there.  hx_kernel_stats kind 7 times the kernels only, not the bitmap upload.
+ * Sidecar: HX_OP_L2 on an engine that keeps the 8-bit row sidecar (hx_create_ex), in query tiles of 1 and 4 (nq < 16, or rows too wide for a
+ * tile of 16), reads the code rows first and fetches only the f32 rows whose proven lower bound does not already lie past the query's running
+ * k-th value; ids, values and counts are bit for bit those without it.  It takes 8 B per query of scratch more (a threshold the
+ * workgroups share) and counts into hx_exact_sidecar_stats.  By default the calls with at least 131 072 passing rows take it (below that the
+ * scan without it measured faster); HX_EXACT_SIDECAR in the environment, read at each call: 0 forces the scan without it, 1 forces
+ * it at every size. */
 enum hx_op { HX_OP_L2 = 0, HX_OP_NEG_IP = 1, HX_OP_COSINE = 2, HX_OP_L1 = 3, HX_OP_HAMMING = 4, HX_OP_JACCARD = 5 };
 #define HX_EXACT_MAX_K 1024
 int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
@@ -249,7 +264,12 @@ int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uin
  * HX_E_ARG: an operator not legal for the dtype, cmp or order out of range, radius NULL with nq > 0, offsets_out or total_out NULL,
  *   ids_out NULL with dist_out not NULL, and the row-range and query-range errors of hx_exact_search.
  * Synchronous on the engine stream; reads only, so it may run while a pipelined index scan (hx_index_search_submit) is in flight.
- * hx_kernel_stats kind 8 times it: units = distances evaluated, ms = summed kernel time (not the uploads and copies); kind 7 is untouched. */
+ * hx_kernel_stats kind 8 times it: units = distances evaluated, ms = summed kernel time (not the uploads and copies); kind 7 is untouched.
+ * Sidecar: HX_OP_L2 with HX_CMP_LT / HX_CMP_LE on an engine that keeps the 8-bit row sidecar, in query tiles of 1 and 4, reads the code rows
+ *   first and fetches only the f32 rows whose proven lower bound does not already fail the comparison; offsets, ids and values are
+ *   bit for bit those without it (count-only calls and the overflow re-scan included).  HX_CMP_GT / HX_CMP_GE never use it.  It counts into
+ *   hx_exact_sidecar_stats.  By default the calls with at least 65 536 passing rows take it; HX_EXACT_SIDECAR in the environment, read at each
+ *   call: 0 forces the scan without it, 1 forces it at every size. */
 enum hx_cmp { HX_CMP_LT = 0, HX_CMP_LE = 1, HX_CMP_GT = 2, HX_CMP_GE = 3 };     /* v <op> q  <  <=  >  >=  radius */
 enum hx_range_order { HX_RANGE_BY_ROW = 0, HX_RANGE_BY_DISTANCE = 1 };
 int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,

@@ -63,6 +63,8 @@ pub const HX_RANGE_BY_DISTANCE: c_int = 1;
 pub const HX_CREATE_SCAN_ONLY: c_int = 1;
 // hx_create_ex flags: no 8-bit row sidecar (f32 L2 engines keep one by default; same results, the searches fetch more f32 rows)
 pub const HX_CREATE_NO_SIDECAR: c_int = 4;
+// hx_create_ex flags: a scan-only f32 L2 engine of more than 128 dimensions keeps the sidecar too (the exact scans skip f32 rows with it)
+pub const HX_CREATE_SCAN_SIDECAR: c_int = 8;
 
 #[link(name = "hnswrx")]
 extern "C" {
@@ -83,6 +85,7 @@ extern "C" {
     pub fn hx_sidecar_read(e: *mut hx_engine, first: u64, n: u64, codes_host: *mut c_void, meta_host: *mut f32) -> c_int;
     pub fn hx_sidecar_stats(e: *mut hx_engine, rows_fetched: *mut u64, rows_rejected: *mut u64, reset: c_int) -> c_int;
     pub fn hx_sidecar_bounds(e: *mut hx_engine, query: u32, ids: *const u32, n: u32, lb_host: *mut f32) -> c_int;
+    pub fn hx_exact_sidecar_stats(e: *mut hx_engine, rows_coded: *mut u64, rows_fetched: *mut u64, reset: c_int) -> c_int;
     pub fn hx_pop_rows(e: *mut hx_engine, n: u64) -> c_int;
     pub fn hx_read_rows(e: *mut hx_engine, first: u64, n: u64, rows_host: *mut c_void) -> c_int;
     pub fn hx_normalize_rows(e: *mut hx_engine, first: u64, n: u64, norms_host: *mut f64) -> c_int;

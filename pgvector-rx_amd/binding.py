@@ -16,6 +16,7 @@ E_NOMEM = -3
 E_RANGE = -7                                           # a value out of range for the target type (the halfvec casts)
 CREATE_SCAN_ONLY = 1                                   # hx_create_ex: no index; vector / halfvec up to 16000 dims
 CREATE_NO_SIDECAR = 4                                  # hx_create_ex: no 8-bit row sidecar (f32 L2 engines keep one by default)
+CREATE_SCAN_SIDECAR = 8                                # hx_create_ex: a scan-only f32 L2 engine (dim > 128) keeps the sidecar for the exact scans
 QUERY_SLOT = 0x80000000
 _NP = {F32: np.float32, F16: np.uint16, BIT: np.uint8, SPARSE: np.uint8}
 SPARSE_MAX_NNZ = 1000
@@ -80,6 +81,7 @@ def lib():
         "hx_sidecar_read": (i32, [vp, u64, u64, vp, vp]),
         "hx_sidecar_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), i32]),
         "hx_sidecar_bounds": (i32, [vp, u32, vp, u32, vp]),
+        "hx_exact_sidecar_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), i32]),
         "hx_normalize_rows": (i32, [vp, u64, u64, vp]),
         "hx_set_queries": (i32, [vp, vp, u32, i32]),
         "hx_set_queries_device": (i32, [vp, vp, u32, i32]),
@@ -191,12 +193,13 @@ def _row_words(row_pass, n_rows, packed):
 class Engine:
     """hx_engine: device row store + batched distance kernels (replaces graph::DistanceFn)."""
 
-    def __init__(self, dtype, metric, dim, capacity, device=0, scan_only=False, sidecar=True):
+    def __init__(self, dtype, metric, dim, capacity, device=0, scan_only=False, sidecar=True, scan_sidecar=False):
         """scan_only: an engine for the scan plans and re-ranking (hx_create_ex HX_CREATE_SCAN_ONLY): vector / halfvec up to 16000 dims,
-        never indexed.  sidecar=False: HX_CREATE_NO_SIDECAR (same results, no 8-bit row copy for the searches to skip rows with)."""
+        never indexed.  sidecar=False: HX_CREATE_NO_SIDECAR (same results, no 8-bit row copy for the searches to skip rows with).
+        scan_sidecar: HX_CREATE_SCAN_SIDECAR, a scan-only f32 L2 engine of more than 128 dims keeps the sidecar for the exact scans."""
         self.dtype, self.metric, self.dim = dtype, metric, dim
         h = C.c_void_p()
-        flags = (CREATE_SCAN_ONLY if scan_only else 0) | (0 if sidecar else CREATE_NO_SIDECAR)
+        flags = (CREATE_SCAN_ONLY if scan_only else 0) | (0 if sidecar else CREATE_NO_SIDECAR) | (CREATE_SCAN_SIDECAR if scan_sidecar else 0)
         rc = lib().hx_create_ex(device, dtype, metric, dim, int(capacity), flags, C.byref(h))
         if rc:
             raise HxError(rc, lib().hx_last_error(None).decode())
@@ -255,6 +258,12 @@ class Engine:
         """(f32 rows the index searches fetched, rows the sidecar bound let them skip) since the last reset"""
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(lib().hx_sidecar_stats(self.h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value
+
+    def exact_sidecar_stats(self, reset=False):
+        """(code rows read, f32 rows read) by the exact_search / exact_range calls that took the sidecar path since the last reset"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(lib().hx_exact_sidecar_stats(self.h, C.byref(a), C.byref(b), int(reset)))
         return a.value, b.value
 
     def sidecar_bounds(self, query, row_ids):

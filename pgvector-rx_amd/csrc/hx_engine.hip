@@ -434,8 +434,10 @@ int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_r
 {
     if (!out) return create_fail(HX_E_ARG, "out is NULL");
     *out = nullptr;
-    if (flags & ~(HX_CREATE_SCAN_ONLY | HX_CREATE_NO_SIDECAR)) return create_fail(HX_E_ARG, "unknown hx_create_ex flags");
+    if (flags & ~(HX_CREATE_SCAN_ONLY | HX_CREATE_NO_SIDECAR | HX_CREATE_SCAN_SIDECAR)) return create_fail(HX_E_ARG, "unknown hx_create_ex flags");
     const bool scan_only = (flags & HX_CREATE_SCAN_ONLY) != 0;
+    if ((flags & HX_CREATE_SCAN_SIDECAR) && (!scan_only || (flags & HX_CREATE_NO_SIDECAR) || dtype != HX_F32 || metric != HX_L2SQ || dim <= 128))
+        return create_fail(HX_E_ARG, "HX_CREATE_SCAN_SIDECAR needs HX_CREATE_SCAN_ONLY on an HX_F32 / HX_L2SQ engine of more than 128 dimensions");
     if (dtype < HX_F32 || dtype > HX_SPARSE) return create_fail(HX_E_ARG, "unknown dtype");
     const bool bit_metric = metric == HX_HAMMING || metric == HX_JACCARD;
     if (metric < HX_L2SQ || metric > HX_JACCARD || bit_metric != (dtype == HX_BIT))
@@ -471,7 +473,8 @@ int hx_create_ex(int device, int dtype, int metric, int dim, uint64_t capacity_r
     CREATE_HIP(hipEventCreate(&e->ev5));
     s = hipMalloc((void **)&e->d_rows, e->capacity * e->pitch);
     if (s != hipSuccess) { hx_destroy(e); return create_fail(HX_E_NOMEM, "cannot reserve row store in HBM"); }
-    if (dtype == HX_F32 && metric == HX_L2SQ && !scan_only && !(flags & HX_CREATE_NO_SIDECAR) && e->pitch > 512) {   // the traversal's 64-lane rows (launch_fused_mode)
+    // the traversal's 64-lane rows (launch_fused_mode); a scan-only engine keeps one only when asked (HX_CREATE_SCAN_SIDECAR: the exact scans use it)
+    if (dtype == HX_F32 && metric == HX_L2SQ && (!scan_only || (flags & HX_CREATE_SCAN_SIDECAR)) && !(flags & HX_CREATE_NO_SIDECAR) && e->pitch > 512) {
         e->sc_pitch = (uint32_t)al16((size_t)dim);
         s = hipMalloc((void **)&e->d_sc_codes, e->capacity * e->sc_pitch);
         if (s == hipSuccess) s = hipMalloc((void **)&e->d_sc_meta, e->capacity * HX_SC_META * sizeof(float));

@@ -14,7 +14,13 @@
 //   and keeps its k best.  Pass 2 (k_exact_merge): one workgroup per query merges the slices' lists the same way in LDS.
 // Sparsevec rows: one lane per (query, row) pair with the merge joins of hx_sparse.hip, feeding the same top-k stage.
 // A filter bitmap is compacted into a row-id list on the device first (k_exact_compact); rows that fail it are never read.
-#include "hx_exact_core.h"
+//
+// <-> on an f32 engine that keeps the 8-bit sidecar (k_exact_scan_sc, query tiles of 1 and 4; hx_exact_sc.h): a round first reads
+//   the code rows, skips the rows whose proven lower bound already lies past the query's threshold key, and queues the survivors' ids in LDS;
+//   the queue is drained through the same ex_eval + append, so the lists are those of k_exact_scan.  The threshold is the smaller of the
+//   workgroup's own k-th key and one key per query shared by all workgroups (atomicMin after every prune), seeded on large inputs by a plain scan
+//   of a prefix of the rows.  Any such key is the k-th key of a subset of the query's rows, hence >= the final k-th key: results do not depend on it.
+#include "hx_exact_sc.h"
 
 namespace {
 
@@ -94,6 +100,113 @@ k_exact_scan(const ExArgs a)
     }
 }
 
+// The sidecar variant for <-> on f32 rows (64 lanes per row).  A round is EX_WAVES * SC_NB wave steps of SC_ROWS code rows; survivors wait in
+// sq[] until a batch of EX_WAVES * RIF is there (or the slice ends) and are then evaluated and appended exactly as in k_exact_scan.
+constexpr int SC_NB = 2, SC_RR = EX_WAVES * SC_NB * SC_ROWS;
+template <class OP, int HOP, int RIF, int Q>
+__global__ void __launch_bounds__(EX_THREADS)
+k_exact_scan_sc(const ExArgs a, const ScArgs c)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t *q_lds = lds;
+    uint64_t *skey = (uint64_t *)(lds + (size_t)Q * a.pitch);
+    uint32_t *sid = (uint32_t *)(skey + a.cap);
+    constexpr int BATCH = EX_WAVES * RIF;
+    __shared__ uint64_t thr_k[Q], T[Q];
+    __shared__ uint32_t thr_i[Q], cnt[Q], sq[SC_RR + BATCH], sq_n;
+    __shared__ float qn[Q];
+    const uint32_t tile = blockIdx.x, s = blockIdx.y;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, g = lane >> 4;
+    uint32_t live = 0;
+#pragma unroll
+    for (int i = 0; i < Q; i++) live |= (tile * Q + i < a.nq ? 1u : 0u) << i;
+
+    ex_park<OP, HOP, Q>(a.queries, a.qslot0, a.nq, tile, a.pitch, a.cap_sp, q_lds, qn, [&] {
+        if (threadIdx.x < Q) {
+            const bool lv = (live >> threadIdx.x) & 1u;
+            thr_k[threadIdx.x] = lv ? ~0ull : 0ull; thr_i[threadIdx.x] = lv ? ~0u : 0u; cnt[threadIdx.x] = 0;
+            T[threadIdx.x] = lv ? __hip_atomic_load(&c.shared[tile * Q + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        }
+        if (threadIdx.x == 0) sq_n = 0;
+    });
+
+    const uint32_t beg = s * a.per, end = beg + a.per < a.n ? beg + a.per : a.n;
+    uint64_t *gkey = a.gkey + ((size_t)tile * a.S + s) * a.cap * Q;
+    uint32_t *gid = a.gid + ((size_t)tile * a.S + s) * a.cap * Q;
+    uint32_t fetched = 0;                                      // thread 0's count of drained rows
+    for (uint32_t b = beg; b < end; b += SC_RR) {
+        for (int nb = 0; nb < SC_NB; nb++) {
+            const uint32_t b0 = b + (wave * SC_NB + nb) * SC_ROWS;
+            if (b0 >= end) break;                              // wave-uniform
+            uint32_t rid[SC_P];
+#pragma unroll
+            for (int p = 0; p < SC_P; p++) {
+                const uint32_t r = b0 + 4u * p + g;
+                rid[p] = a.ids ? a.ids[r < end ? r : beg] : a.row0 + (r < end ? r : beg);   // slots past the slice re-read its first row; never kept
+            }
+            const uint32_t m = sc_survivors<Q>(c, q_lds, rid, end - b0 < (uint32_t)SC_ROWS ? end - b0 : (uint32_t)SC_ROWS, T, live, lane);
+            if (m) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&sq_n, (uint32_t)__popc(m));
+                base = __shfl(base, 0, 64);
+                if (lane < (uint32_t)SC_ROWS && ((m >> lane) & 1u))
+                    sq[base + __popc(m & ((1u << lane) - 1u))] = a.ids ? a.ids[b0 + lane] : a.row0 + b0 + lane;
+            }
+        }
+        __syncthreads();
+        const uint32_t n = sq_n;
+        if (n >= (uint32_t)BATCH || (b + SC_RR >= end && n > 0)) {
+            for (uint32_t o = 0; o < n; o += BATCH) {
+                uint32_t rid[RIF]; bool ok[RIF]; const uint8_t *rp[RIF];
+#pragma unroll
+                for (int j = 0; j < RIF; j++) {
+                    const uint32_t x = o + wave * RIF + j;
+                    ok[j] = x < n;
+                    rid[j] = sq[ok[j] ? x : 0];                // slots past the queue re-read its first row; never appended
+                    rp[j] = a.rows + (size_t)rid[j] * a.pitch;
+                }
+                auto append = [&](int i, int j, double v) {
+                    const uint64_t key = ex_key(v);
+                    if (lane == 0 && ok[j] && ex_less(key, rid[j], thr_k[i], thr_i[i])) {
+                        const uint32_t pos = atomicAdd(&cnt[i], 1u);
+                        gkey[pos * Q + i] = key; gid[pos * Q + i] = rid[j];
+                    }
+                };
+                ex_eval<OP, HOP, 64, RIF, Q>(q_lds, qn, rp, a.pitch, a.cap_sp, lane, append);
+                __syncthreads();
+                for (int i = 0; i < Q; i++)
+                    if (cnt[i] > a.cap - BATCH) {
+                        ex_prune(gkey + i, gid + i, Q, skey, sid, a.k, &cnt[i], &thr_k[i], &thr_i[i]);
+                        if (threadIdx.x == 0) atomicMin((unsigned long long *)&c.shared[tile * Q + i], (unsigned long long)thr_k[i]);   // ~0 until k entries
+                    }
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) { fetched += n; sq_n = 0; }
+        }
+        if (threadIdx.x < Q && ((live >> threadIdx.x) & 1u)) {
+            const uint64_t sh = __hip_atomic_load(&c.shared[tile * Q + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            T[threadIdx.x] = sh < thr_k[threadIdx.x] ? sh : thr_k[threadIdx.x];
+        }
+        __syncthreads();
+    }
+    for (int i = 0; i < Q; i++) {
+        if (tile * Q + i >= a.nq) break;
+        if (cnt[i] > a.k) ex_prune(gkey + i, gid + i, Q, skey, sid, a.k, &cnt[i], &thr_k[i], &thr_i[i]);
+        if (threadIdx.x == 0) {
+            a.gcnt[(size_t)(tile * Q + i) * a.S + s] = cnt[i];
+            atomicMin((unsigned long long *)&c.shared[tile * Q + i], (unsigned long long)thr_k[i]);
+        }
+    }
+    if (threadIdx.x == 0) { atomicAdd(c.stats, (unsigned long long)(end - beg)); atomicAdd(c.stats + 1, (unsigned long long)fetched); }
+}
+
+// the seed of the shared thresholds: the k-th key of a finished top-k (of a prefix of the rows), where that has k entries
+__global__ void k_exact_seed(const uint32_t *__restrict__ cnt, const double *__restrict__ dist, uint32_t k, uint32_t nq, uint64_t *__restrict__ shared)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq && cnt[q] == k) shared[q] = ex_key(dist[(size_t)q * k + k - 1]);
+}
+
 // one workgroup per query: the S slice lists (each <= k entries, at stride cap) in chunks of cap2 / 2 positions through an LDS buffer
 __global__ void __launch_bounds__(EX_MERGE_THREADS)
 k_exact_merge(const uint64_t *__restrict__ gkey, const uint32_t *__restrict__ gid, const uint32_t *__restrict__ gcnt, uint32_t S, uint32_t cap, uint32_t Q,
@@ -141,6 +254,7 @@ __global__ void k_exact_compact(const uint64_t *__restrict__ words, uint64_t n_w
 }
 
 struct ExPlan { uint32_t Q, R, cap, S, per, nqb, cap2; };
+constexpr uint32_t EX_SEED_ROWS = 16384;                      // prefix of the rows whose top k seeds the sidecar path's shared thresholds
 
 template <class OP, int HOP, int LPR, int RIF, int Q>
 hipError_t ex_launch_scan(hx_engine *e, const ExArgs &a, uint32_t tiles)
@@ -154,6 +268,21 @@ hipError_t ex_launch_scan(hx_engine *e, const ExArgs &a, uint32_t tiles)
         attr_devices |= bit;
     }
     hipLaunchKernelGGL((k_exact_scan<OP, HOP, LPR, RIF, Q>), dim3(tiles, a.S), dim3(EX_THREADS), lds, e->stream, a);
+    return hipGetLastError();
+}
+
+template <int RIF, int Q>
+hipError_t ex_launch_scan_sc(hx_engine *e, const ExArgs &a, const ScArgs &c, uint32_t tiles)
+{
+    const size_t lds = (size_t)Q * a.pitch + (size_t)a.cap * 12;
+    static thread_local uint64_t attr_devices = 0;
+    const uint64_t bit = 1ull << (e->device & 63);
+    if (lds > 60 * 1024 && !(attr_devices & bit)) {
+        hipError_t s = hipFuncSetAttribute((const void *)k_exact_scan_sc<OpF32<K_L2>, HX_OP_L2, RIF, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+        if (s != hipSuccess) return s;
+        attr_devices |= bit;
+    }
+    hipLaunchKernelGGL((k_exact_scan_sc<OpF32<K_L2>, HX_OP_L2, RIF, Q>), dim3(tiles, a.S), dim3(EX_THREADS), lds, e->stream, a, c);
     return hipGetLastError();
 }
 
@@ -264,7 +393,10 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
     const size_t nq_pad = (size_t)(p.nqb + p.Q - 1) / p.Q * p.Q;            // the buffers are laid out by whole query tiles
     const size_t o_id = o_key + al16(nq_pad * p.S * p.cap * 8), o_cnt = o_id + al16(nq_pad * p.S * p.cap * 4);
     const size_t o_oid = o_cnt + al16((size_t)p.nqb * p.S * 4), o_od = o_oid + al16((size_t)p.nqb * k * 4), o_oc = o_od + al16((size_t)p.nqb * k * 8);
-    const size_t need = o_oc + al16((size_t)p.nqb * 4);
+    // the sidecar path (<-> on an engine with a sidecar, query tiles of 1 and 4): 8 B per query for the shared threshold key, and two counters
+    const bool sc = op == HX_OP_L2 && e->d_sc_codes && p.Q <= 4 && sc_enabled(n_pass, SC_MIN_ROWS_TOPK);
+    const size_t o_sh = o_oc + al16((size_t)p.nqb * 4), o_st = o_sh + (sc ? al16(nq_pad * 8) : 0);
+    const size_t need = o_st + (sc ? 16 : 0);
     if (need > e->cap_exact) {
         if (e->d_exact) (void)hipFree(e->d_exact);
         e->d_exact = nullptr; e->cap_exact = 0;
@@ -289,11 +421,37 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
     a.rows = e->d_rows; a.queries = e->d_queries; a.pitch = pitch; a.cap_sp = (uint32_t)std::min(e->dim, HX_SPARSE_MAX_NNZ);
     a.ids = d_ids; a.row0 = (uint32_t)first_row; a.n = (uint32_t)n_pass; a.per = p.per; a.S = p.S; a.k = k; a.cap = p.cap;
     a.gkey = (uint64_t *)(d + o_key); a.gid = (uint32_t *)(d + o_id); a.gcnt = (uint32_t *)(d + o_cnt);
+    ScArgs c{};
+    unsigned long long sc_stats[2] = {0, 0}; uint64_t seed_rows = 0;
+    // seed: large inputs first take the top k of a prefix with the plain kernel (no threshold is known yet, so every row of it would be fetched
+    // anyway); its k-th key starts the shared thresholds, so the main scan skips from its first round on
+    const uint32_t n_seed = sc && n_pass >= SC_MIN_ROWS_TOPK && k <= EX_SEED_ROWS / 8 ? EX_SEED_ROWS : 0;
+    if (sc) {
+        c.codes = e->d_sc_codes; c.meta = e->d_sc_meta; c.cpitch = e->sc_pitch; c.dim = (uint32_t)e->dim; c.nterm = pitch >> 2;
+        c.shared = (uint64_t *)(d + o_sh); c.stats = (unsigned long long *)(d + o_st);
+        HX_HIP(e, hipMemsetAsync(d + o_st, 0, 16, e->stream));
+    }
     for (uint32_t q0 = 0; q0 < nq; q0 += p.nqb) {
-        const uint32_t nb = std::min(p.nqb, nq - q0);
+        const uint32_t nb = std::min(p.nqb, nq - q0), tiles = (nb + p.Q - 1) / p.Q;
         if (q0 > 0 && e->timing) HX_HIP(e, hipEventRecord(e->ev0, e->stream));
         a.qslot0 = first_query + q0; a.nq = nb;
-        HX_HIP(e, ex_scan(e, op, a, p.Q, (nb + p.Q - 1) / p.Q));
+        if (sc) {
+            HX_HIP(e, hipMemsetAsync(d + o_sh, 0xFF, nq_pad * 8, e->stream));
+            if (n_seed) {
+                ExArgs as = a;
+                as.S = std::min<uint32_t>(p.S, n_seed / (4 * p.R)); as.per = (n_seed + as.S - 1) / as.S; as.S = (n_seed + as.per - 1) / as.per; as.n = n_seed;
+                HX_HIP(e, ex_scan(e, op, as, p.Q, tiles));
+                hipLaunchKernelGGL(k_exact_merge, dim3(nb), dim3(EX_MERGE_THREADS), (size_t)p.cap2 * 12, e->stream, as.gkey, as.gid, as.gcnt, as.S, p.cap, p.Q, k, p.cap2,
+                                   0, (uint32_t *)(d + o_oid), (double *)(d + o_od), (uint32_t *)(d + o_oc));
+                HX_HIP(e, hipGetLastError());
+                hipLaunchKernelGGL(k_exact_seed, dim3((nb + 255) / 256), dim3(256), 0, e->stream, (const uint32_t *)(d + o_oc), (const double *)(d + o_od), k, nb, c.shared);
+                HX_HIP(e, hipGetLastError());
+                launches += 3; seed_rows += (uint64_t)n_seed * tiles;
+            }
+            HX_HIP(e, (p.Q == 4 ? ex_launch_scan_sc<4, 4>(e, a, c, tiles) : ex_launch_scan_sc<4, 1>(e, a, c, tiles)));
+        } else {
+            HX_HIP(e, ex_scan(e, op, a, p.Q, tiles));
+        }
         hipLaunchKernelGGL(k_exact_merge, dim3(nb), dim3(EX_MERGE_THREADS), (size_t)p.cap2 * 12, e->stream, a.gkey, a.gid, a.gcnt, p.S, p.cap, p.Q, k, p.cap2,
                            (int)(op == HX_OP_NEG_IP), (uint32_t *)(d + o_oid), (double *)(d + o_od), (uint32_t *)(d + o_oc));
         HX_HIP(e, hipGetLastError());
@@ -302,12 +460,23 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
         HX_HIP(e, hipMemcpyAsync(ids_out + (size_t)q0 * k, d + o_oid, (size_t)nb * k * 4, hipMemcpyDeviceToHost, e->stream));
         HX_HIP(e, hipMemcpyAsync(dist_out + (size_t)q0 * k, d + o_od, (size_t)nb * k * 8, hipMemcpyDeviceToHost, e->stream));
         HX_HIP(e, hipMemcpyAsync(counts_out + q0, d + o_oc, (size_t)nb * 4, hipMemcpyDeviceToHost, e->stream));
+        if (sc) HX_HIP(e, hipMemcpyAsync(sc_stats, d + o_st, 16, hipMemcpyDeviceToHost, e->stream));   // running totals of this call
         HX_HIP(e, hipStreamSynchronize(e->stream));
         if (e->timing) { float t = 0.f; HX_HIP(e, hipEventElapsedTime(&t, e->ev0, e->ev1)); ms += t; }
     }
+    e->xs_coded += sc_stats[0]; e->xs_fetched += sc_stats[1] + seed_rows;
     if (e->timing) {
         e->last_ms = (float)ms;
         e->stat_exact.launches += launches; e->stat_exact.units += n_pass * nq; e->stat_exact.ms += ms;
     }
+    return HX_OK;
+}
+
+extern "C" int hx_exact_sidecar_stats(hx_engine *e, uint64_t *rows_coded, uint64_t *rows_fetched, int reset)
+{
+    if (!e) return HX_E_ARG;
+    if (rows_coded) *rows_coded = e->xs_coded;
+    if (rows_fetched) *rows_fetched = e->xs_fetched;
+    if (reset) e->xs_coded = e->xs_fetched = 0;
     return HX_OK;
 }

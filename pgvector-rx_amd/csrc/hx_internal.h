@@ -127,6 +127,7 @@ struct hx_engine {
     // 8-bit row sidecar (hx_sidecar.hip): f32 L2 engines with 64-lane rows, unless HX_CREATE_NO_SIDECAR.  codes [capacity][sc_pitch],
     // {lo, step, e_x, 0} per row; sc_rows / sc_rej: f32 rows the traversal fetched / rows the bound rejected (hx_sidecar_stats)
     uint8_t *d_sc_codes = nullptr; float *d_sc_meta = nullptr; uint32_t sc_pitch = 0; uint64_t sc_rows = 0, sc_rej = 0;
+    uint64_t xs_coded = 0, xs_fetched = 0;                    // exact / range scans on the sidecar path: code rows and f32 rows read (hx_exact_sidecar_stats)
     // pipelined scans: launches overlap, so their busy time is the UNION of the launches' [start, end] intervals (HIP events of each slot's stream,
     // measured from ev_scan_epoch on the engine's stream); stat_scan.ms = that union
     HxKernelStat stat_scan; hipEvent_t ev_scan_epoch = nullptr; bool scan_epoch_set = false; double scan_last_end = 0.0;

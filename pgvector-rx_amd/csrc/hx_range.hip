@@ -15,7 +15,11 @@
 //   values keep row order.
 // A filter bitmap is compacted into a row-id list in row order (per-word offsets: popcount + exclusive scan, then k_range_compact);
 // rows that fail it are never read.
-#include "hx_exact_core.h"
+//
+// <-> with `<` / `<=` on an f32 engine that keeps the 8-bit sidecar (k_range_scan_sc, query tiles of 1 and 4; hx_exact_sc.h): a wave
+//   first reads the code rows of SC_ROWS rows and evaluates only those whose proven lower bound does not already lie past the radius, in row
+//   order, through the same ex_eval and ballot + prefix count.  Count-only calls and the window pass take the same kernel.
+#include "hx_exact_sc.h"
 
 #include <hipcub/hipcub.hpp>
 #include <vector>
@@ -114,6 +118,101 @@ k_range_scan(const RgArgs a)
     }
 }
 
+// The sidecar variant for <-> `<` / `<=` on f32 rows (64 lanes per row): the threshold key of query i is khi[i], nothing is shared.
+template <class OP, int HOP, int RIF, int Q>
+__global__ void __launch_bounds__(EX_THREADS)
+k_range_scan_sc(const RgArgs a, const ScArgs c)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t *q_lds = lds;
+    __shared__ float qn[Q];
+    __shared__ uint64_t klo[Q], khi[Q], dbase[EX_WAVES][Q];
+    __shared__ uint32_t plo[EX_WAVES][Q], phi[EX_WAVES][Q], st_coded, st_fetched;
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t g = blockIdx.y * EX_WAVES + wave;
+    const bool window = a.seg_base != nullptr;
+    uint32_t live = 0;
+#pragma unroll
+    for (int i = 0; i < Q; i++) live |= (tile * Q + i < a.nq ? 1u : 0u) << i;
+
+    ex_park<OP, HOP, Q>(a.queries, a.qslot0, a.nq, tile, a.pitch, a.cap_sp, q_lds, qn, [&] {
+        if (threadIdx.x == 0) { st_coded = 0; st_fetched = 0; }
+        if (lane < Q) {                                        // as k_range_scan
+            const uint32_t q = tile * Q + lane;
+            const bool lv = q < a.nq;
+            if (wave == 0) { klo[lane] = lv ? a.klo[q] : ~0ull; khi[lane] = lv ? a.khi[q] : 0ull; }
+            uint64_t db = 0; uint32_t lo = 0, hi = 0;
+            if (lv && a.oid) {
+                const size_t seg = (size_t)q * a.G + g;
+                if (!window) { db = seg * a.scap; hi = a.scap; }
+                else if (a.cnt[seg] > a.scap) {
+                    const uint64_t sb = a.seg_base[seg], n = a.cnt[seg];
+                    db = sb - a.w0;
+                    lo = (uint32_t)(sb < a.w0 ? std::min<uint64_t>(n, a.w0 - sb) : 0);
+                    hi = (uint32_t)(sb < a.w1 ? std::min<uint64_t>(n, a.w1 - sb) : 0);
+                }
+            }
+            dbase[wave][lane] = db; plo[wave][lane] = lo; phi[wave][lane] = hi;
+        }
+    });
+
+    const uint32_t beg = (uint32_t)std::min<uint64_t>((uint64_t)g * a.wper, a.n);
+    uint32_t end = (uint32_t)std::min<uint64_t>((uint64_t)beg + a.wper, a.n);
+    if (window) {                                              // nothing of this wave's in the window: no row is read
+        bool any = false;
+        for (int i = 0; i < Q; i++) any |= plo[wave][i] < phi[wave][i];
+        if (!any) end = beg;
+    }
+    uint32_t cnt[Q], nf = 0;
+#pragma unroll
+    for (int i = 0; i < Q; i++) cnt[i] = 0;
+    for (uint32_t b = beg; b < end; b += SC_ROWS) {
+        uint32_t rid4[SC_P];
+#pragma unroll
+        for (int p = 0; p < SC_P; p++) {
+            const uint32_t r = b + 4u * p + (lane >> 4);
+            rid4[p] = a.ids ? a.ids[r < end ? r : beg] : a.row0 + (r < end ? r : beg);
+        }
+        uint32_t m = sc_survivors<Q>(c, q_lds, rid4, end - b < (uint32_t)SC_ROWS ? end - b : (uint32_t)SC_ROWS, khi, live, lane);
+        nf += (uint32_t)__popc(m);
+        while (m) {                                            // survivors in row order, RIF at a time
+            uint32_t rid[RIF]; bool ok[RIF]; const uint8_t *rp[RIF];
+#pragma unroll
+            for (int j = 0; j < RIF; j++) {
+                ok[j] = m != 0;
+                const uint32_t r = ok[j] ? b + (uint32_t)__builtin_ctz(m) : beg;   // slots past the survivors re-read the segment's first row; never hits
+                m &= m - 1u;
+                rid[j] = a.ids ? a.ids[r] : a.row0 + r;
+                rp[j] = a.rows + (size_t)rid[j] * a.pitch;
+            }
+            auto emit = [&](int i, int j, double v) {          // one row per slot: lane 0 holds its value
+                const uint64_t key = ex_key(v);
+                const bool hit = lane == 0 && ok[j] && klo[i] <= key && key <= khi[i];
+                if (hit) {
+                    const uint32_t pos = cnt[i];
+                    if (pos >= plo[wave][i] && pos < phi[wave][i]) {
+                        const size_t d = (size_t)(dbase[wave][i] + pos);
+                        a.oid[d] = rid[j];
+                        if (a.okey) a.okey[d] = key;
+                    }
+                }
+                cnt[i] += (uint32_t)__popcll(__ballot(hit));
+            };
+            ex_eval<OP, HOP, 64, RIF, Q>(q_lds, qn, rp, a.pitch, a.cap_sp, lane, emit);
+        }
+    }
+    if (lane == 0) {
+        if (!window) {
+#pragma unroll
+            for (int i = 0; i < Q; i++)
+                if (tile * Q + i < a.nq) a.cnt[(size_t)(tile * Q + i) * a.G + g] = cnt[i];
+        }
+        atomicAdd(&st_coded, end - beg); atomicAdd(&st_fetched, nf);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { atomicAdd(c.stats, (unsigned long long)st_coded); atomicAdd(c.stats + 1, (unsigned long long)st_fetched); }
+}
+
 // the staged segments that did not overflow, each to its CSR position when that lies in [w0, w1); one wave per segment
 __global__ void __launch_bounds__(256)
 k_range_gather(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sid, const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ seg_base,
@@ -164,6 +263,20 @@ hipError_t rg_launch(hx_engine *e, const RgArgs &a, uint32_t tiles)
         attr_devices |= bit;
     }
     hipLaunchKernelGGL((k_range_scan<OP, HOP, LPR, RIF, Q>), dim3(tiles, a.G / EX_WAVES), dim3(EX_THREADS), lds, e->stream, a);
+    return hipGetLastError();
+}
+template <int RIF, int Q>
+hipError_t rg_launch_sc(hx_engine *e, const RgArgs &a, const ScArgs &c, uint32_t tiles)
+{
+    const size_t lds = (size_t)Q * a.pitch;
+    static thread_local uint64_t attr_devices = 0;
+    const uint64_t bit = 1ull << (e->device & 63);
+    if (lds > 60 * 1024 && !(attr_devices & bit)) {
+        hipError_t s = hipFuncSetAttribute((const void *)k_range_scan_sc<OpF32<K_L2>, HX_OP_L2, RIF, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+        if (s != hipSuccess) return s;
+        attr_devices |= bit;
+    }
+    hipLaunchKernelGGL((k_range_scan_sc<OpF32<K_L2>, HX_OP_L2, RIF, Q>), dim3(tiles, a.G / EX_WAVES), dim3(EX_THREADS), lds, e->stream, a, c);
     return hipGetLastError();
 }
 template <class OP, int HOP, int LPR>
@@ -294,7 +407,9 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
         if (W == 0) return e->fail(HX_E_NOMEM, "HX_RANGE_SCRATCH leaves no room for the output window");
     }
     const size_t o_okey = o_out, o_oid = o_okey + (need_key ? al16(W * 8) : 0), o_okey2 = o_oid + al16(W * 4), o_oid2 = o_okey2 + (by_dist ? al16(W * 8) : 0);
-    const size_t o_tmp = o_oid2 + (by_dist ? al16(W * 4) : 0), need = o_tmp + al16(tmp_bytes) + 16;
+    // the sidecar path (<-> with `<` / `<=` on an engine with a sidecar, query tiles of 1 and 4): two counters behind the scratch
+    const bool sc = op == HX_OP_L2 && (cmp == HX_CMP_LT || cmp == HX_CMP_LE) && e->d_sc_codes && Q <= 4 && sc_enabled(n_pass, SC_MIN_ROWS_RANGE);
+    const size_t o_tmp = o_oid2 + (by_dist ? al16(W * 4) : 0), o_st = o_tmp + al16(tmp_bytes) + 16, need = o_st + (sc ? 16 : 0);
     if (need > e->cap_range) {
         if (e->d_range) (void)hipFree(e->d_range);
         e->d_range = nullptr; e->cap_range = 0;
@@ -330,6 +445,17 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
     a.ids = row_pass ? (const uint32_t *)d : nullptr; a.row0 = (uint32_t)first_row; a.n = (uint32_t)n_pass; a.wper = wper; a.G = G;
     a.klo = (const uint64_t *)(d + o_klo); a.khi = (const uint64_t *)(d + o_khi); a.cnt = (uint32_t *)(d + o_cnt);
     uint64_t *d_base = (uint64_t *)(d + o_base);
+    ScArgs c{};
+    unsigned long long sc_stats[2] = {0, 0};
+    if (sc) {
+        c.codes = e->d_sc_codes; c.meta = e->d_sc_meta; c.cpitch = e->sc_pitch; c.dim = (uint32_t)e->dim; c.nterm = pitch >> 2;
+        c.stats = (unsigned long long *)(d + o_st);
+        HX_HIP(e, hipMemsetAsync(d + o_st, 0, 16, e->stream));
+    }
+    auto scan = [&](const RgArgs &ra, uint32_t tiles) -> hipError_t {
+        if (!sc) return rg_scan(e, op, ra, Q, tiles);
+        return Q == 4 ? rg_launch_sc<4, 4>(e, ra, c, tiles) : rg_launch_sc<4, 1>(e, ra, c, tiles);
+    };
     std::vector<uint64_t> klo(nqb), khi(nqb), base(nseg);
     std::vector<uint32_t> cnt(nseg);
     std::vector<int> qoff(nqb + 1);
@@ -344,10 +470,11 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
         a.qslot0 = first_query + q0; a.nq = nb; a.scap = writing ? scap : 0; a.seg_base = nullptr; a.w0 = a.w1 = 0;
         a.okey = writing && need_key ? (uint64_t *)(d + o_skey) : nullptr; a.oid = writing ? (uint32_t *)(d + o_sid) : nullptr;
         HX_HIP(e, t_begin());
-        HX_HIP(e, rg_scan(e, op, a, Q, tiles));
+        HX_HIP(e, scan(a, tiles));
         HX_HIP(e, t_end());
         launches++;
         HX_HIP(e, hipMemcpyAsync(cnt.data(), a.cnt, (size_t)nb * G * 4, hipMemcpyDeviceToHost, e->stream));
+        if (sc) HX_HIP(e, hipMemcpyAsync(sc_stats, d + o_st, 16, hipMemcpyDeviceToHost, e->stream));   // running totals of this call
         HX_HIP(e, hipStreamSynchronize(e->stream));
         HX_HIP(e, t_add());
         uint64_t pos = 0; bool overflow = false;                 // CSR positions relative to the block's first hit
@@ -386,7 +513,7 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
             if (rescan) {                                        // the overflowed segments' hits in this window, straight to their positions
                 RgArgs b = a;
                 b.scap = scap; b.seg_base = d_base; b.w0 = w0; b.w1 = w1; b.okey = okey; b.oid = oid;
-                HX_HIP(e, rg_scan(e, op, b, Q, tiles));
+                HX_HIP(e, scan(b, tiles));
                 launches++;
             }
             const uint64_t wn = w1 - w0;
@@ -406,12 +533,14 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
             HX_HIP(e, t_end());
             HX_HIP(e, hipMemcpyAsync(ids_out + blk0 + w0, oid, wn * 4, hipMemcpyDeviceToHost, e->stream));
             if (dist_out) HX_HIP(e, hipMemcpyAsync(dist_out + blk0 + w0, okey, wn * 8, hipMemcpyDeviceToHost, e->stream));
+            if (sc && rescan) HX_HIP(e, hipMemcpyAsync(sc_stats, d + o_st, 16, hipMemcpyDeviceToHost, e->stream));
             HX_HIP(e, hipStreamSynchronize(e->stream));
             HX_HIP(e, t_add());
             w0 = w1; qa = qb;
         }
     }
     *total_out = offsets_out[nq];
+    e->xs_coded += sc_stats[0]; e->xs_fetched += sc_stats[1];
     if (e->timing) {
         e->last_ms = (float)ms;
         e->stat_range.launches += launches; e->stat_range.units += n_pass * nq; e->stat_range.ms += ms;

@@ -4,8 +4,8 @@
 #include "hx_fused_core.h"
 
 // One wave per row: lo / hi over the row, codes c_i = rint((x_i - lo) / step) clamped to [0, 255], then e_x from x^_i = fmaf(step, c_i, lo) -- the
-// kernels' own expression -- as an f64 sum of squares, widened by 2^-40 (the f64 rounding of <= 2000 squares, their sum and the root) and rounded
-// up to f32.  A row with a non-finite value, range, step or x^_i gets e_x = +inf: its bound is always 0.  Codes past dim (up to the pitch) are 0.
+// kernels' own expression -- as an f64 sum of squares, widened by 2^-40 (the f64 rounding of <= 2000 squares, their sum and the root; by 2^-36 for
+// the up to 16000 squares of a scan-only engine's rows past 2000 dimensions) and rounded up to f32.  A row with a non-finite value, range, step or x^_i gets e_x = +inf: its bound is always 0.  Codes past dim (up to the pitch) are 0.
 __global__ void __launch_bounds__(256) k_sc_encode(const uint8_t *rows, uint32_t pitch, uint32_t dim, uint64_t first, uint64_t n, uint8_t *codes, uint32_t cpitch, float *meta)
 {
     const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) k_sc_encode(const uint8_t *rows, uint32_t
     }
     for (int o = 32; o >= 1; o >>= 1) err += __shfl_xor(err, o, 64);
     ok = ok && __all(fx) != 0;
-    const double e = sqrt(err) * (1.0 + 0x1p-40);
+    const double e = sqrt(err) * (dim > 2000u ? 1.0 + 0x1p-36 : 1.0 + 0x1p-40);
     float ex = (float)e;
     if ((double)ex < e) ex = nextafterf(ex, __builtin_inff());
     if (!ok || !__builtin_isfinite(ex)) ex = __builtin_inff();

@@ -8,7 +8,10 @@ then one line each for halfvec(4000) <#>, vector(1536) <=> and bit(1024) <~> (nq
 none / 1 %.  Each line: kernel time (hx_kernel_stats kind 7, one warm-up call, median of R calls) and wall time; algorithmic bytes = passing
 rows x row payload (each read once), GB/s and fraction of the 8 TB/s HBM peak; distance evaluations per second.  The nq = 1, k = 10, unfiltered
 vector(768) line also times, for comparison, the oracle's brute force on one CPU core (sequential sums, over the first 100 000 rows, scaled to N)
-and bench.py's torch ground_truth formula |r|^2 - 2 q.r on the same device rows -- different arithmetic from the operator's, labelled so."""
+and bench.py's torch ground_truth formula |r|^2 - 2 q.r on the same device rows -- different arithmetic from the operator's, labelled so.
+Where the call took the 8-bit sidecar path, rows_fetched_frac = f32 rows read / code rows read, bytes_moved_model = code rows x
+(al16(dim) + 16) + f32 rows x row bytes, and hbm_peak_frac is computed from that model (`bytes` stays the rows' payload); kernel_ms_min / _max
+are the extremes of the R calls."""
 import argparse
 import json
 import os
@@ -36,22 +39,27 @@ def device_rows(torch, n, dim, dtype, seed):
 def measure(e, op, k, nq, mask, reps):
     e.exact_search(op, k, nq=nq, row_pass=mask)                     # warm-up (scratch reservation, code objects)
     ks, ws = [], []
+    e.exact_sidecar_stats(reset=True)
     for _ in range(reps):
         e.kernel_stats(7, reset=True)
         t = time.perf_counter()
         e.exact_search(op, k, nq=nq, row_pass=mask)
         ws.append((time.perf_counter() - t) * 1e3)
         ks.append(e.kernel_stats(7)["ms"])
-    return float(np.median(ks)), float(np.median(ws))
+    coded, fetched = e.exact_sidecar_stats(reset=True)
+    return float(np.median(ks)), float(np.median(ws)), min(ks), max(ks), coded / reps, fetched / reps
 
 
 def line(shape, e, dtype, dim, op, n, nq, k, filt, mask, reps, row_bytes):
     n_pass = int(mask.sum()) if mask is not None else n
-    kms, wms = measure(e, op, k, nq, mask, reps)
+    kms, wms, kmin, kmax, coded, fetched = measure(e, op, k, nq, mask, reps)
     nbytes = n_pass * row_bytes
+    moved = coded * ((dim + 15) // 16 * 16 + 16) + fetched * row_bytes if coded else nbytes
     out = {"shape": shape, "rows": n, "dim": dim, "op": op, "nq": nq, "k": k, "filter": filt, "passing_rows": n_pass,
            "kernel_ms": round(kms, 4), "wall_ms": round(wms, 4), "bytes": nbytes, "gbps": round(nbytes / kms / 1e6, 1),
-           "hbm_peak_frac": round(nbytes / kms / 1e-3 / HBM_PEAK, 3), "dist_per_s": float("%.4g" % (n_pass * nq / kms * 1e3))}
+           "hbm_peak_frac": round(moved / kms / 1e-3 / HBM_PEAK, 3), "dist_per_s": float("%.4g" % (n_pass * nq / kms * 1e3)),
+           "kernel_ms_min": round(kmin, 4), "kernel_ms_max": round(kmax, 4),
+           "rows_fetched_frac": round(fetched / coded, 4) if coded else None, "bytes_moved_model": int(moved)}
     return out
 
 

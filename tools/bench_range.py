@@ -7,7 +7,9 @@ Shapes: N x vector(768) f32 <-> (default N = 1 000 000) for nq in {1, 16, 256}, 
 (the values of hx_exact_search's k-th neighbour, or a quantile of a sample), each by row, by distance and count-only; then halfvec(4000) <#>
 and bit(1024) <~> for one line each (nq 1, ~1 000 hits, by row).  --quick: nq {1, 16}, ~10 and ~1 000 hits.  Each line: kernel time
 (hx_kernel_stats kind 8, one warm-up call, median of R calls) and wall time; algorithmic bytes = rows x row payload (each row read once per
-query tile) plus 12 B per hit written; GB/s and fraction of the 8 TB/s HBM peak; hits per second."""
+query tile) plus 12 B per hit written; GB/s and fraction of the 8 TB/s HBM peak; hits per second.  Where the call took the 8-bit sidecar path
+(DESIGN.md 3a), rows_fetched_frac = f32 rows read / code rows read, bytes_moved_model = code rows x (al16(dim) + 16) + f32 rows x row bytes
+(+ the hits), and hbm_peak_frac is computed from that model (`bytes` stays the rows' payload); kernel_ms_min / _max: extremes of the R calls."""
 import argparse
 import json
 import os
@@ -48,23 +50,28 @@ def measure(e, op, r, nq, mode, reps):
     out = e.exact_range(op, r, nq=nq, **kw)                     # warm-up (scratch reservation, code objects)
     cap = max(1, int(out[0][-1]))
     ks, ws = [], []
+    e.exact_sidecar_stats(reset=True)
     for _ in range(reps):
         e.kernel_stats(8, reset=True)
         t = time.perf_counter()
         e.exact_range(op, r, nq=nq, cap=None if kw["count_only"] else cap, **kw)
         ws.append((time.perf_counter() - t) * 1e3)
         ks.append(e.kernel_stats(8)["ms"])
-    return float(np.median(ks)), float(np.median(ws)), int(out[0][-1])
+    coded, fetched = e.exact_sidecar_stats(reset=True)
+    return float(np.median(ks)), float(np.median(ws)), int(out[0][-1]), min(ks), max(ks), coded / reps, fetched / reps
 
 
 def line(shape, e, dim, op, n, nq, hits, mode, r, reps, row_bytes):
-    kms, wms, total = measure(e, op, r, nq, mode, reps)
+    kms, wms, total, kmin, kmax, coded, fetched = measure(e, op, r, nq, mode, reps)
     tiles = (nq + 15) // 16 if nq >= 16 and 16 * row_bytes <= 65536 else (nq + 3) // 4 if nq >= 4 and 4 * row_bytes <= 65536 else nq
     nbytes = n * row_bytes * tiles + (0 if mode == "count_only" else total * 12)
+    hit_bytes = 0 if mode == "count_only" else total * 12
+    moved = coded * ((dim + 15) // 16 * 16 + 16) + fetched * row_bytes + hit_bytes if coded else nbytes
     return {"shape": shape, "rows": n, "dim": dim, "op": op, "nq": nq, "target_hits_per_query": hits, "mode": mode, "hits": total,
             "kernel_ms": round(kms, 4), "wall_ms": round(wms, 4), "bytes": nbytes, "gbps": round(nbytes / kms / 1e6, 1),
-            "hbm_peak_frac": round(nbytes / kms / 1e-3 / HBM_PEAK, 3), "hits_per_s": float("%.4g" % (total / kms * 1e3)),
-            "dist_per_s": float("%.4g" % (n * nq / kms * 1e3))}
+            "hbm_peak_frac": round(moved / kms / 1e-3 / HBM_PEAK, 3), "hits_per_s": float("%.4g" % (total / kms * 1e3)),
+            "dist_per_s": float("%.4g" % (n * nq / kms * 1e3)), "kernel_ms_min": round(kmin, 4), "kernel_ms_max": round(kmax, 4),
+            "rows_fetched_frac": round(fetched / coded, 4) if coded else None, "bytes_moved_model": int(moved)}
 
 
 def main():
