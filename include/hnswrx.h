@@ -453,6 +453,37 @@ int hx_index_search_iterative(hx_index *ix, uint32_t nq, uint32_t ef_search, int
                               uint32_t limit, const uint8_t *filter_pass, uint64_t n_filter,
                               int64_t *tids_out, float *dist_out, uint32_t *counts_out);
 
+/* The iterative scan with a WHERE clause per query: `WHERE <cond> AND v <op> q <cmp> r ORDER BY v <op> q LIMIT k` for nq backends in one
+ * launch.  mode (1 / 2 only), ef_search, max_scan_tuples, limit, the query slots 0..nq-1 and the output layout are those of
+ * hx_index_search_iterative; elems_out (nullable) receives the element of each tuple.  A plain scan (iterative_scan = off) never resumes, so its
+ * host filters the dist_out of hx_index_search itself.
+ *   Filters: filters[f] is a filter_pass array as above (indexed by heap TID, filter_len[f] entries, a TID past the end fails); query q uses
+ *     filters[filter_of[q]], filter_of[q] == -1 or filter_of == NULL: every TID passes.  At most HX_SCAN_MAX_FILTERS per call; the device holds
+ *     2 bytes per filter and element for the call.
+ *   Distance predicate: cmp == -1: none; else (enum hx_cmp) a heap tuple of query q passes when `value <cmp> radius[q]` holds under PostgreSQL's
+ *     float8 comparison exactly as hx_exact_range defines it (-0.0 == +0.0; NaN equal to NaN and above everything, so `< NaN` passes every
+ *     non-NaN value).  value is the operator function's float8 result formed from THE f32 DISTANCE THIS SCAN RETURNS for the tuple in dist_out:
+ *     sqrt((double)d) on an HX_L2SQ index (<->), (double)d on HX_NEG_IP (<#>), HX_L1 (<+>) and HX_HAMMING (<~>) -- bit for bit what
+ *     hx_exact_search returns for the pair.  On the cosine operator classes (HX_NEG_IP over normalised rows) the predicate is therefore on <#> of
+ *     the normalised rows, not on <=>.  HX_JACCARD indexes return HX_E_ARG for cmp != -1 (their f32 is a rounding of the float8 operator value).
+ *   A tuple keeps its place in the reference's loop: it is counted, the strict_order test and its update of the previous distance come first
+ *     (scan.rs:796-815), then filter and predicate reject it as the executor would: a rejected tuple is consumed, not returned.
+ *   flags: HX_SCAN_STOP_PAST_RADIUS (mode 2 with HX_CMP_LT / HX_CMP_LE only, HX_E_ARG otherwise).  In strict_order the distances that survive
+ *     the order test never decrease and value is monotone in d, so once a surviving tuple's value is not NaN and fails the predicate no later
+ *     tuple can pass: the query ends there instead of resuming until max_scan_tuples (which is what the reference does: its executor cannot
+ *     tell the access method).  Outputs are those of the call without the flag as long as no distance of the scan is NaN -- a NaN resets the
+ *     order test (scan.rs:801-806), after which nearer tuples could still be returned.  Off by default.
+ * Errors: HX_E_ARG for a bad mode, max_scan_tuples < 1, n_filters > HX_SCAN_MAX_FILTERS, filter_of[q] outside [-1, n_filters), cmp out of range,
+ * radius == NULL with cmp != -1, an unknown or illegal flag, NULL outputs; HX_E_STATE as hx_index_search_iterative. */
+#define HX_SCAN_MAX_FILTERS 64
+#define HX_SCAN_STOP_PAST_RADIUS 1
+int hx_index_search_filtered(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
+                             uint32_t n_filters, const uint8_t *const *filters, const uint64_t *filter_len,
+                             const int32_t *filter_of,          /* nq entries, -1 = no filter; NULL = none for all */
+                             int cmp, const double *radius,     /* cmp: -1 = no predicate, else enum hx_cmp; radius[nq] */
+                             int flags,
+                             int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out);
+
 /* One scan with a NULL order-by value (`ORDER BY val <-> NULL`; scan.rs:186-187: every element gets distance 0.0, the distance procedure is
  * never called).  Pure graph traversal on the host -- there is nothing to compute -- in the order Rust's BinaryHeap gives equal keys.
  * mode 0: plain scan (k = limit), 1 / 2: iterative as above.  tids_out / elems_out (may be NULL): `limit` entries; *count_out = tuples returned. */

@@ -56,6 +56,8 @@ pub const HX_CMP_LT: c_int = 0; // <
 pub const HX_CMP_LE: c_int = 1; // <=
 pub const HX_CMP_GT: c_int = 2; // >
 pub const HX_CMP_GE: c_int = 3; // >=
+pub const HX_SCAN_MAX_FILTERS: u32 = 64; // filters per hx_index_search_filtered call
+pub const HX_SCAN_STOP_PAST_RADIUS: c_int = 1; // strict_order with < / <=: end a query at the first tuple past its radius
 // hx_range_order: heap order (WHERE only) or the ORDER BY without LIMIT
 pub const HX_RANGE_BY_ROW: c_int = 0;
 pub const HX_RANGE_BY_DISTANCE: c_int = 1;
@@ -179,6 +181,12 @@ extern "C" {
     pub fn hx_index_search_iterative(ix: *mut hx_index, nq: u32, ef_search: u32, mode: c_int, max_scan_tuples: i64, limit: u32,
                                      filter_pass: *const u8, n_filter: u64, tids_out: *mut i64, dist_out: *mut f32,
                                      counts_out: *mut u32) -> c_int;
+    /// Iterative scan with a WHERE clause per query (include/hnswrx.h): `filters[filter_of[q]]` (-1 / null: none) and `value cmp radius[q]`
+    /// (cmp: -1 = no predicate, else HX_CMP_*); flags: HX_SCAN_STOP_PAST_RADIUS.
+    pub fn hx_index_search_filtered(ix: *mut hx_index, nq: u32, ef_search: u32, mode: c_int, max_scan_tuples: i64, limit: u32,
+                                    n_filters: u32, filters: *const *const u8, filter_len: *const u64, filter_of: *const i32,
+                                    cmp: c_int, radius: *const f64, flags: c_int, tids_out: *mut i64, dist_out: *mut f32,
+                                    elems_out: *mut u32, counts_out: *mut u32) -> c_int;
     /// `ORDER BY val <-> NULL` (scan.rs:186-187): traversal with every distance 0.0, no kernel involved.
     pub fn hx_index_search_null(ix: *mut hx_index, ef_search: u32, mode: c_int, max_scan_tuples: i64, limit: u32, filter_pass: *const u8,
                                 n_filter: u64, tids_out: *mut i64, elems_out: *mut u32, count_out: *mut u32) -> c_int;

@@ -13,6 +13,7 @@
 //! This is the *minimal* drop-in (one launch per expansion: correct, but latency-bound); the intended one hands whole
 //! batches to `hx_index_insert` / `hx_index_search`, which run these same functions on the device.
 use std::collections::{BinaryHeap, HashSet};
+use std::os::raw::c_int;
 
 use super::ffi::*;
 use crate::graph::{Candidate, ElementIdx, FurthestCandidate, GraphElement, NearestCandidate};
@@ -249,4 +250,71 @@ pub fn update_neighbor_connections_gpu(gpu: GpuDistance, elements: &mut [GraphEl
             elements[*target].neighbors[lc as usize].items = select_on_table(all, lm, &table);
         }
     }
+}
+
+/// The WHERE clause of one backend's query in a shared launch of `hx_index_search_filtered`.
+pub struct ScanWhere<'a> {
+    /// `filter_pass` by heap TID (`None`: every tuple passes); backends with the same clause may share one slice.
+    pub filter: Option<&'a [u8]>,
+    /// Right-hand side of `v <op> q <cmp> r`; ignored when the call has no predicate.
+    pub radius: f64,
+}
+
+/// What `amgettuple` hands out for one query: heap TIDs nearest first with the f32 distances of the scan.
+pub struct ScanTuples {
+    pub tids: Vec<i64>,
+    pub distances: Vec<f32>,
+}
+
+/// `WHERE cond AND v <op> q <cmp> r ORDER BY v <op> q LIMIT limit` for the engine's query slots `0..clauses.len()` in one launch
+/// (iterative scan; `mode` 1 = relaxed_order, 2 = strict_order).  `cmp`: `None` or `Some(HX_CMP_*)`; `stop_past_radius` is legal
+/// with strict_order and `<` / `<=` only (include/hnswrx.h).  Identical filter slices are uploaded once.
+pub fn search_filtered_gpu(
+    ix: *mut hx_index,
+    clauses: &[ScanWhere],
+    ef_search: u32,
+    mode: c_int,
+    max_scan_tuples: i64,
+    limit: u32,
+    cmp: Option<c_int>,
+    stop_past_radius: bool,
+) -> Vec<ScanTuples> {
+    let nq = clauses.len();
+    let mut filters: Vec<*const u8> = Vec::new();
+    let mut filter_len: Vec<u64> = Vec::new();
+    let mut filter_of: Vec<i32> = Vec::with_capacity(nq);
+    for c in clauses {
+        match c.filter {
+            None => filter_of.push(-1),
+            Some(f) => {
+                let at = filters.iter().zip(filter_len.iter()).position(|(&p, &l)| p == f.as_ptr() && l == f.len() as u64);
+                let at = at.unwrap_or_else(|| {
+                    filters.push(f.as_ptr());
+                    filter_len.push(f.len() as u64);
+                    filters.len() - 1
+                });
+                filter_of.push(at as i32);
+            }
+        }
+    }
+    assert!(filters.len() <= HX_SCAN_MAX_FILTERS as usize, "split the launch: more than HX_SCAN_MAX_FILTERS distinct filters");
+    let radius: Vec<f64> = clauses.iter().map(|c| c.radius).collect();
+    let mut tids = vec![0i64; nq * limit as usize];
+    let mut dist = vec![0f32; nq * limit as usize];
+    let mut counts = vec![0u32; nq];
+    unsafe {
+        ck_index(
+            ix,
+            hx_index_search_filtered(ix, nq as u32, ef_search, mode, max_scan_tuples, limit, filters.len() as u32, filters.as_ptr(),
+                                     filter_len.as_ptr(), filter_of.as_ptr(), cmp.unwrap_or(-1), radius.as_ptr(),
+                                     if stop_past_radius { HX_SCAN_STOP_PAST_RADIUS } else { 0 }, tids.as_mut_ptr(), dist.as_mut_ptr(),
+                                     std::ptr::null_mut(), counts.as_mut_ptr()),
+        );
+    }
+    (0..nq)
+        .map(|q| {
+            let (a, b) = (q * limit as usize, q * limit as usize + counts[q] as usize);
+            ScanTuples { tids: tids[a..b].to_vec(), distances: dist[a..b].to_vec() }
+        })
+        .collect()
 }

@@ -11,6 +11,7 @@ L2SQ, NEG_IP, L1, HAMMING, JACCARD = 0, 1, 2, 3, 4
 OP_L2, OP_NEG_IP, OP_COSINE, OP_L1, OP_HAMMING, OP_JACCARD = 0, 1, 2, 3, 4, 5   # hx_op: the SQL operators <-> <#> <=> <+> <~> <%>
 EXACT_MAX_K = 1024
 CMP_LT, CMP_LE, CMP_GT, CMP_GE = 0, 1, 2, 3           # hx_cmp: v <op> q  <  <=  >  >=  radius
+SCAN_MAX_FILTERS, SCAN_STOP_PAST_RADIUS = 64, 1       # hx_index_search_filtered
 RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap order, or the ORDER BY without LIMIT
 E_NOMEM = -3
 E_RANGE = -7                                           # a value out of range for the target type (the halfvec casts)
@@ -148,6 +149,7 @@ def lib():
         "hx_index_search_submit": (i32, [vp, u32, u32, u32, u32, u32]),
         "hx_index_search_wait": (i32, [vp, u32, vp, vp, vp, vp]),
         "hx_index_search_iterative": (i32, [vp, u32, u32, i32, i64, u32, vp, u64, vp, vp, vp]),
+        "hx_index_search_filtered": (i32, [vp, u32, u32, i32, i64, u32, u32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
         "hx_index_search_null": (i32, [vp, u32, i32, i64, u32, vp, u64, vp, vp, vp]),
         "hx_index_serialize_pages": (i32, [vp, vp, u64, C.POINTER(u64), vp, vp]),
         "hx_index_load_pages": (i32, [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]),
@@ -733,3 +735,24 @@ class Index:
                                                  0 if f is None else len(f), _p(tids), _p(d), _p(cnt)))
         self._pad(cnt, limit, (tids, -1), (d, np.inf))
         return tids, d, cnt
+
+    def search_filtered(self, nq, ef_search, mode, max_scan_tuples, limit, filters=None, filter_of=None, cmp=None, radius=None,
+                        stop_past_radius=False):
+        """Iterative scan with a WHERE clause per query (hx_index_search_filtered): query q is filtered by filters[filter_of[q]] (-1: none) and
+        by `value <cmp> radius[q]` (cmp: one of CMP_LT / CMP_LE / CMP_GT / CMP_GE, None: no predicate).  Returns (tids, distances, elements, counts)."""
+        tids = np.empty((nq, limit), np.int64)
+        d = np.empty((nq, limit), np.float32)
+        el = np.empty((nq, limit), np.uint32)
+        cnt = np.zeros(nq, np.uint32)
+        fl = [np.ascontiguousarray(f, np.uint8) for f in (filters or [])]
+        ptrs = (C.c_void_p * max(len(fl), 1))(*[f.ctypes.data for f in fl])
+        lens = np.array([len(f) for f in fl], np.uint64)
+        fo = None if filter_of is None else np.ascontiguousarray(filter_of, np.int32)
+        if fo is not None and len(fo) != nq:
+            raise ValueError("filter_of needs one entry per query")
+        r = None if radius is None else np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (nq,)))
+        self._ck(lib().hx_index_search_filtered(self.h, nq, ef_search, mode, max_scan_tuples, limit, len(fl), C.cast(ptrs, C.c_void_p) if fl else None,
+                                                _p(lens) if fl else None, _p(fo), -1 if cmp is None else int(cmp), _p(r),
+                                                SCAN_STOP_PAST_RADIUS if stop_past_radius else 0, _p(tids), _p(d), _p(el), _p(cnt)))
+        self._pad(cnt, limit, (tids, -1), (d, np.inf), (el, 0))
+        return tids, d, el, cnt

@@ -240,13 +240,15 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
             HX_HIP(this, hipMalloc((void **)&mr.d_disc, need_disc));
             mr.cap_disc = need_disc;
         }
-        if (mr.cap > mr.cap_emask) {
+        // the mask table: one row of n_elems masks per filter of the call (one row: a mirror's worth, as before), allocated once and reused
+        const uint64_t need_em = std::max<uint64_t>(mr.cap, (uint64_t)std::max<uint32_t>(it->mask_rows, 1u) * it->n_elems);
+        if (need_em > mr.cap_emask) {
             if (mr.d_emask) (void)hipFree(mr.d_emask);
             mr.d_emask = nullptr; mr.cap_emask = 0;
-            HX_HIP(this, hipMalloc((void **)&mr.d_emask, (size_t)mr.cap * 2));
-            mr.cap_emask = mr.cap;
+            HX_HIP(this, hipMalloc((void **)&mr.d_emask, (size_t)need_em * 2));
+            mr.cap_emask = need_em;
         }
-        HX_HIP(this, hipMemcpyAsync(mr.d_emask, it->emask, (size_t)it->n_elems * 2, hipMemcpyHostToDevice, stream));
+        HX_HIP(this, hipMemcpyAsync(mr.d_emask, it->emask, (size_t)std::max<uint32_t>(it->mask_rows, 1u) * it->n_elems * 2, hipMemcpyHostToDevice, stream));
     }
     if (!io.d_spill) HX_HIP(this, hipMalloc((void **)&io.d_spill, (size_t)256 * FUSED_SLOTS_PER_CU * FUSED_CCAP * 8));
     uint32_t *vis_ptr = nullptr; void *spill_ptr = io.d_spill;
@@ -268,7 +270,8 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
     const size_t out_n = dev ? 0 : !ins ? (size_t)ntasks * k : (size_t)ntasks * FUSED_MAXL * 2 * mr.m;      // mode 2: k = limit
     const size_t cnt_n = dev ? 0 : !ins ? (size_t)ntasks : (size_t)ntasks * FUSED_MAXL;
     // device task/in/out buffers (one allocation, reused)
-    const size_t need = al16((size_t)ntasks * 4) * 6 + al16(out_n * 4) * 3 + al16(cnt_n * 4) + 256;
+    const size_t frow_n = (mode == 2 && it->t_frow) ? (size_t)ntasks : 0, key_n = (mode == 2 && it->t_key) ? (size_t)ntasks * 2 : 0;   // per-query filter row / predicate interval
+    const size_t need = al16((size_t)ntasks * 4) * 6 + al16(frow_n * 4) + al16(key_n * 4) + al16(out_n * 4) * 3 + al16(cnt_n * 4) + 256;
     if (need > io.cap_io) {
         if (io.d_io) (void)hipFree(io.d_io);
         if (io.h_io) (void)hipHostFree(io.h_io);
@@ -285,6 +288,8 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
     const size_t o_slot = o; o += al16((size_t)ntasks * 4);
     const size_t o_prob = o; o += al16((size_t)ntasks * 4);
     const size_t o_ent = o; o += al16((size_t)ntasks * 4);
+    const size_t o_key = o; o += al16(key_n * 4);
+    const size_t o_frow = o; o += al16(frow_n * 4);
     const size_t in_bytes = o;
     const size_t o_st = o; o += al16((size_t)ntasks * 4);
     const size_t o_cnt = o; o += al16(cnt_n * 4);
@@ -297,6 +302,8 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
     if (dev && dev->h_slots) memcpy(io.h_io + o_slot, dev->h_slots, (size_t)ntasks * 4);
     if (mode == 3) memcpy(io.h_io + o_prob, dev->h_prob, (size_t)ntasks * 4);
     if (mode == 3 && dev->h_entry) memcpy(io.h_io + o_ent, dev->h_entry, (size_t)ntasks * 4);
+    if (key_n) memcpy(io.h_io + o_key, it->t_key, key_n * 4);
+    if (frow_n) memcpy(io.h_io + o_frow, it->t_frow, frow_n * 4);
     HX_HIP(this, hipMemcpyAsync(io.d_io, io.h_io, in_bytes, hipMemcpyHostToDevice, stream));
     FusedParams p;
     p.rows = d_rows; p.queries = d_queries; p.pitch = (uint32_t)pitch; p.nch = (uint32_t)((pitch + 1023) / 1024); p.n_rows = n_rows;
@@ -306,7 +313,11 @@ int hx_engine::fused_launch(HxFusedIo &io, int mode, uint32_t ntasks, const uint
     p.ntasks = ntasks; p.t_qsel = (const uint32_t *)(io.d_io + o_q); p.t_level = (const int32_t *)(io.d_io + o_lv);
     p.ef = ef; p.k = k; p.ccap = ccap; p.clds = clds; p.wcap = wcap;
     p.iter_mode = 0; p.limit = k; p.max_tuples = 0; p.emask = nullptr; p.disc = nullptr; p.disc_stride = 0; p.disc_lds = disc_lds; p.out_tix = (uint32_t *)(io.d_io + o_tix);
-    if (mode == 2) { p.iter_mode = (uint32_t)it->iter_mode; p.max_tuples = it->max_tuples; p.emask = mr.d_emask; p.disc = (unsigned long long *)mr.d_disc; p.disc_stride = (uint32_t)disc_stride; }
+    p.emask_stride = 0; p.iter_flags = 0; p.t_frow = nullptr; p.t_key = nullptr;
+    if (mode == 2) { p.iter_mode = (uint32_t)it->iter_mode; p.max_tuples = it->max_tuples; p.emask = mr.d_emask; p.disc = (unsigned long long *)mr.d_disc; p.disc_stride = (uint32_t)disc_stride;
+                     p.emask_stride = (uint32_t)it->n_elems; p.iter_flags = (it->val_sqrt ? 1u : 0u) | (it->stop_past ? 2u : 0u);
+                     if (frow_n) p.t_frow = (const uint32_t *)(io.d_io + o_frow);
+                     if (key_n) p.t_key = (const uint32_t *)(io.d_io + o_key); }
     p.spill = (uint2 *)spill_ptr; p.spill_stride = ccap;
     { const char *dv = getenv("HX_F_DBG"); p.fdbg = dv ? (uint32_t)atoi(dv) : 0u; }
     p.sa = sa ? 1u : 0u;

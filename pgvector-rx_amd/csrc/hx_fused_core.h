@@ -76,6 +76,11 @@ struct FusedParams {
     // 8-bit row sidecar (f32 L2, 64 lanes per row; nullptr: off): codes [n_rows][sc_pitch], {lo, step, e_x, 0} per row (hx_ops.h).
     // n_dist[17] = f32 rows fetched by the searches, n_dist[18] = rows the bound rejected before their f32 row was fetched
     const uint8_t *sc_codes; const float *sc_meta; uint32_t sc_pitch, dim;
+    // MODE 2 with per-query filters and a distance predicate (hx_index_search_filtered).  emask is a table of rows emask_stride elements apart, task
+    // t reads row t_frow[t] (nullptr: row 0); a tuple passes when t_key[2t] <= hx_order_key32(d, iter_flags & 1) <= t_key[2t + 1] (nullptr:
+    // no predicate; iter_flags bit 0: the operator's value is sqrt((double)d)).  iter_flags bit 1 (strict_order with < / <=): the first tuple that survives
+    // the order test with a non-NaN value past t_key[2t + 1] ends the query -- the distances that survive never decrease, so nothing later can pass.
+    uint32_t emask_stride, iter_flags; const uint32_t *t_frow; const uint32_t *t_key;
 };
 
 // The traversal kernels read their parameter block IN PLACE from the kernarg segment (constant address space: scalar loads), through a

@@ -562,18 +562,34 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
                     if (!single) f_sort_results(cx, wl, true);                                   // EP[0..wl): nearest LAST
                     // emit from the back (scan.rs:796-815, 860-874); the elements' TID masks are fetched 64 at a time
                     uint32_t left = wl;
-                    while (left > 0 && outc < p.limit) {
+                    // The query's WHERE clause: its row of the mask table and the interval of f32 order keys its distance predicate comes to (the host
+                    // maps `value <cmp> radius` onto the returned f32, hx_index.cpp: where_keys32).  Fetched per emit phase into scalar registers
+                    // (every lane holds the same task) through a fresh view of the parameters, so nothing of them is live across the search above.
+                    KParams &pw = f_params_here(p);
+                    const uint32_t tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+                    const uint32_t frow = pw.t_frow ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pw.t_frow[tu]) : 0u;
+                    const uint16_t *const em_row = pw.emask + (size_t)frow * pw.emask_stride;
+                    const uint32_t wflags = pw.iter_flags;
+                    uint32_t klo = 0u, khi = ~0u;
+                    if (pw.t_key) { klo = (uint32_t)__builtin_amdgcn_readfirstlane((int)pw.t_key[2u * tu]); khi = (uint32_t)__builtin_amdgcn_readfirstlane((int)pw.t_key[2u * tu + 1u]); }
+                    bool past = false;                                                           // HX_SCAN_STOP_PAST_RADIUS: nothing further can pass
+                    while (left > 0 && outc < p.limit && !past) {
                         const uint32_t c = left < 64u ? left : 64u, base = left - c;
-                        if (lane < c) cx.IDS[lane] = p.emask[cx.EP[base + lane].y];
+                        if (lane < c) cx.IDS[lane] = em_row[cx.EP[base + lane].y];
                         F_BAR();
-                        for (uint32_t i = c; i-- > 0 && outc < p.limit;) {
+                        for (uint32_t i = c; i-- > 0 && outc < p.limit && !past;) {
                             const uint32_t em = cx.IDS[i]; const uint32_t nt = em >> 12;
                             if (nt == 0) continue;                                               // scan.rs:866-868
                             tuples++;
                             const uint2 v = cx.EP[base + i]; const double dv = (double)fh_d(v);
+                            // order key of the returned f32 distance (one per element: wave-uniform); ~0: the operator's value is NaN
+                            const uint32_t key = hx_order_key32(fh_d(v), (wflags & 1u) != 0u);
+                            const bool in_range = key >= klo && key <= khi;
+                            const bool beyond = (wflags & 2u) != 0u && key > khi && key != ~0u;
                             for (int ti = (int)nt - 1; ti >= 0 && outc < p.limit; ti--) {        // heaptids.pop()
                                 if (p.iter_mode == 2u) { if (dv < prev) continue; prev = dv; }   // strict_order, scan.rs:801-806
-                                if (!((em >> ti) & 1u)) continue;                                // the executor's filter rejects this tuple
+                                if (beyond) { past = true; break; }                              // survived the order test, not NaN, past the radius
+                                if (!((em >> ti) & 1u) || !in_range) continue;                   // the executor's filter rejects this tuple
                                 if (lane == 0) { p.out_ids[obase + outc] = v.y; p.out_d[obase + outc] = fh_d(v); p.out_tix[obase + outc] = (uint32_t)ti; }
                                 outc++;
                             }
@@ -581,7 +597,7 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
                         F_BAR();
                         left = base;
                     }
-                    if (outc >= p.limit) break;
+                    if (outc >= p.limit || past) break;
                     if (tuples >= p.max_tuples) {                                                // scan.rs:831-841: drain `discarded` one by one
                         if (cx.dlen == 0) break;
                         const uint2 one = PHeap<true>::pop(cx.DS, cx.dlen, lane);

@@ -529,6 +529,8 @@ struct BacklinkTask : LsTask {
 struct QueryTask : LsTask {
     const Graph *g; uint32_t slot; size_t ef_search; int mode; int64_t max_scan_tuples; uint32_t limit;
     const uint8_t *filter = nullptr; uint64_t n_filter = 0;
+    // distance predicate of hx_index_search_filtered: the tuple passes when klo <= hx_order_key(value) <= khi; stop_past: HX_SCAN_STOP_PAST_RADIUS
+    bool has_pred = false, val_sqrt = false, stop_past = false, past = false; uint64_t klo = 0, khi = ~0ull;
     enum { Q_INIT, Q_ENTRY, Q_GREEDY, Q_GROUND, Q_EMIT, Q_RESUME, Q_DONE } st = Q_INIT;
     int lc = 0;
     std::vector<Cand> ep, results;        // results: nearest LAST
@@ -577,19 +579,23 @@ struct QueryTask : LsTask {
                 st = Q_EMIT;
                 break;
             case Q_EMIT:                                                             // scan.rs:794-875
-                while (!results.empty() && out_tid.size() < limit) {
+                while (!results.empty() && out_tid.size() < limit && !past) {
                     const Cand scd = results.back(); results.pop_back();
                     const uint8_t nt = g->ntids[scd.id];
                     if (nt == 0) continue;                                           // scan.rs:866-868
                     tuples++;
+                    // the operator's float8 value of the returned f32 distance, as its order key (the kernel's emit loop does the same)
+                    const uint64_t key = has_pred ? hx_order_key(val_sqrt ? std::sqrt((double)scd.d) : (double)scd.d) : 0ull;
+                    const bool in_range = key >= klo && key <= khi, beyond = stop_past && key > khi && key != ~0ull;
                     for (int t = (int)nt - 1; t >= 0 && out_tid.size() < limit; t--) {   // heaptids.pop()
                         if (mode == 2) { if ((double)scd.d < previous_distance) continue; previous_distance = (double)scd.d; }
+                        if (beyond) { past = true; break; }                          // survived the order test, not NaN, past the radius: nothing later can pass
                         const int64_t tid = g->tids[scd.id][t];
-                        if (!pass(tid)) continue;
+                        if (!pass(tid) || !in_range) continue;
                         out_tid.push_back(tid); out_d.push_back(scd.d); out_elem.push_back(scd.id);
                     }
                 }
-                if (out_tid.size() >= limit || !iterative) { st = Q_DONE; break; }
+                if (out_tid.size() >= limit || !iterative || past) { st = Q_DONE; break; }
                 // results exhausted, iterative scan: scan.rs:817-858
                 if (tuples >= max_scan_tuples) {
                     Cand one;
@@ -2512,8 +2518,33 @@ int hx_index_counters(const hx_index *ix, uint64_t counters_out[8])
 }
 
 // the scans `todo` (indices into the caller's output arrays; engine query slot = q0 + index) on the lock-step host driver
+// The WHERE clause of each query of an iterative scan (hx_index_search_filtered): query q is filtered by filters[filter_of[q]] (-1 / no
+// filter_of: every TID passes) and by keys[2q] <= hx_order_key(value) <= keys[2q + 1] (no keys: no predicate).  keys32: the same predicate as an
+// interval of the returned f32's order keys (where_keys32), which is what the traversal kernel tests; the lock-step driver evaluates the value itself.
+struct ScanWhere {
+    uint32_t n_filters = 0; const uint8_t *const *filters = nullptr; const uint64_t *filter_len = nullptr; const int32_t *filter_of = nullptr;
+    const uint64_t *keys = nullptr; const uint32_t *keys32 = nullptr; bool val_sqrt = false, stop_past = false;
+    int fidx(uint32_t q) const { return (n_filters && filter_of) ? filter_of[q] : -1; }
+};
+
+// The f32 distances whose operator value lies in the key interval [lo, hi]: K(k) = hx_order_key(value of the f32 with order key k) never decreases
+// over k (hx_order_key32: the value is (double)d or sqrt((double)d), both monotone in d, and every d without a value is at the top key), so they
+// are the f32 keys from the first k with K(k) >= lo to the last with K(k) <= hi -- two binary searches.  Empty: {~0, 0}.
+static void where_keys32(uint64_t lo, uint64_t hi, bool root, uint32_t out[2])
+{
+    auto K = [&](uint64_t k) -> uint64_t {
+        const uint32_t b = (k >> 31) ? (uint32_t)k ^ 0x80000000u : ~(uint32_t)k;
+        const float d = __builtin_bit_cast(float, b);
+        return hx_order_key32(d, root) == ~0u ? ~0ull : hx_order_key(root ? std::sqrt((double)d) : (double)d);
+    };
+    const uint64_t kmin = root ? 0x80000000ull : 0x007FFFFFull, kend = 0x100000000ull;     // from 0 (root) / -inf; kend: one past the NaN key
+    auto first_where = [&](auto pred) { uint64_t a = kmin, b = kend; while (a < b) { const uint64_t m = (a + b) >> 1; if (pred(K(m))) b = m; else a = m + 1; } return a; };
+    const uint64_t l = first_where([&](uint64_t v) { return v >= lo; }), h = first_where([&](uint64_t v) { return v > hi; });
+    if (l >= h) { out[0] = ~0u; out[1] = 0u; } else { out[0] = (uint32_t)l; out[1] = (uint32_t)(h - 1); }
+}
+
 static int lockstep_scan(hx_index *ix, const std::vector<uint32_t> &todo, uint32_t q0, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
-                         const uint8_t *filter, uint64_t n_filter, int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
+                         const ScanWhere &w, int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
 {
     const uint32_t nt = (uint32_t)todo.size();
     std::vector<std::unique_ptr<QueryTask>> &qs = ix->query_pool; std::vector<LsTask *> tasks(nt);
@@ -2524,7 +2555,11 @@ static int lockstep_scan(hx_index *ix, const std::vector<uint32_t> &todo, uint32
         t.st = QueryTask::Q_INIT; t.lc = 0; t.n_dist = t.n_pair = 0; t.clear_req(); t.tuples = 0; t.previous_distance = -HUGE_VAL;
         t.out_tid.clear(); t.out_d.clear(); t.out_elem.clear(); t.discarded.clear(); t.results.clear();
         t.g = &ix->g; t.slot = q0 + q; t.ef_search = ef_search; t.mode = mode; t.max_scan_tuples = max_scan_tuples; t.limit = limit;
-        t.filter = filter; t.n_filter = n_filter;
+        const int f = w.fidx(q);
+        t.filter = f < 0 ? nullptr : w.filters[f]; t.n_filter = f < 0 ? 0 : w.filter_len[f];
+        if (t.filter == nullptr && f >= 0) { static const uint8_t none = 0; t.filter = &none; t.n_filter = 0; }   // an empty filter passes nothing
+        t.has_pred = w.keys != nullptr; t.klo = w.keys ? w.keys[2 * (size_t)q] : 0; t.khi = w.keys ? w.keys[2 * (size_t)q + 1] : ~0ull;
+        t.val_sqrt = w.val_sqrt; t.stop_past = w.stop_past; t.past = false;
         tasks[qi] = &t;
     }
     int rc = ix->run_lockstep(tasks);
@@ -2607,7 +2642,7 @@ static int finish_device_scan(hx_index *ix, const HxFusedView &v, uint32_t q0, u
 }
 
 static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
-                       const uint8_t *filter, uint64_t n_filter, int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
+                       const ScanWhere &w, int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
 {
     if (!ix) return HX_E_ARG;
     if (nq == 0) return HX_OK;
@@ -2640,18 +2675,29 @@ static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, 
         if (rc) return rc;
         const Graph &g = ix->g;
         const uint32_t n = g.size();
-        std::vector<uint16_t> emask(n);
+        // The mask table: one row per filter of the call, in front of them an "every TID passes" row when some query has no filter.  One shared
+        // filter (hx_index_search_iterative) or none is a single row, and the tasks carry no row index.
+        bool unfiltered = w.n_filters == 0;
+        for (uint32_t q = 0; q < nq && !unfiltered; q++) unfiltered = w.fidx(q) < 0;
+        const uint32_t row0 = unfiltered ? 1u : 0u, mask_rows = row0 + w.n_filters;
+        std::vector<uint16_t> emask((size_t)mask_rows * n);
         ix->pool->parallel_for((n + 65535) / 65536, [&](size_t ci) {
             for (size_t el = ci * 65536; el < std::min<size_t>(n, ci * 65536 + 65536); el++) {
-                const uint32_t nt = g.level[el] < 0 ? 0u : g.ntids[el]; uint32_t msk = 0;
-                for (uint32_t t = 0; t < nt; t++) { const int64_t tid = g.tids[el][t]; if (!filter || (tid >= 0 && (uint64_t)tid < n_filter && filter[tid])) msk |= 1u << t; }
-                emask[el] = (uint16_t)(msk | (nt << 12));
+                const uint32_t nt = g.level[el] < 0 ? 0u : g.ntids[el];
+                if (row0) emask[el] = (uint16_t)(((1u << nt) - 1u) | (nt << 12));
+                for (uint32_t f = 0; f < w.n_filters; f++) {
+                    const uint8_t *filter = w.filters[f]; const uint64_t n_filter = filter ? w.filter_len[f] : 0; uint32_t msk = 0;
+                    for (uint32_t t = 0; t < nt; t++) { const int64_t tid = g.tids[el][t]; if (tid >= 0 && (uint64_t)tid < n_filter && filter[tid]) msk |= 1u << t; }
+                    emask[(size_t)(row0 + f) * n + el] = (uint16_t)(msk | (nt << 12));
+                }
             }
         });
-        std::vector<uint32_t> qsel(nq), status(nq), ocnt(nq), oids((size_t)nq * limit), otix((size_t)nq * limit);
+        std::vector<uint32_t> qsel(nq), status(nq), ocnt(nq), oids((size_t)nq * limit), otix((size_t)nq * limit), frow;
         std::vector<float> od((size_t)nq * limit);
         for (uint32_t q = 0; q < nq; q++) qsel[q] = HX_QUERY_SLOT | q;
-        HxFusedIter it; it.iter_mode = mode; it.max_tuples = max_scan_tuples; it.emask = emask.data(); it.n_elems = n; it.out_tix = otix.data();
+        if (mask_rows > 1) { frow.resize(nq); for (uint32_t q = 0; q < nq; q++) { const int f = w.fidx(q); frow[q] = f < 0 ? 0u : row0 + (uint32_t)f; } }
+        HxFusedIter it; it.iter_mode = mode; it.max_tuples = max_scan_tuples; it.emask = emask.data(); it.n_elems = n; it.mask_rows = mask_rows; it.out_tix = otix.data();
+        it.t_frow = frow.empty() ? nullptr : frow.data(); it.t_key = w.keys32; it.val_sqrt = w.val_sqrt; it.stop_past = w.stop_past;
         uint64_t cnts[2] = {0, 0};
         auto t0 = std::chrono::steady_clock::now();
         if ((rc = ix->e->fused_run(2, nq, qsel.data(), nullptr, ef_search, limit, (uint32_t)g.entry, g.level[g.entry],
@@ -2676,7 +2722,10 @@ static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, 
             const uint32_t na = (uint32_t)again.size();
             std::vector<uint32_t> q2(na), st2(na), c2(na), i2((size_t)na * limit), x2((size_t)na * limit); std::vector<float> d2((size_t)na * limit);
             for (uint32_t k = 0; k < na; k++) q2[k] = HX_QUERY_SLOT | again[k];
-            HxFusedIter it2 = it; it2.out_tix = x2.data();
+            std::vector<uint32_t> f2, k2;                   // the redone queries keep their filter row and predicate
+            if (it.t_frow) { f2.resize(na); for (uint32_t k = 0; k < na; k++) f2[k] = it.t_frow[again[k]]; }
+            if (it.t_key) { k2.resize(2 * (size_t)na); for (uint32_t k = 0; k < na; k++) { k2[2 * (size_t)k] = it.t_key[2 * (size_t)again[k]]; k2[2 * (size_t)k + 1] = it.t_key[2 * (size_t)again[k] + 1]; } }
+            HxFusedIter it2 = it; it2.out_tix = x2.data(); it2.t_frow = it.t_frow ? f2.data() : nullptr; it2.t_key = it.t_key ? k2.data() : nullptr;
             if ((rc = ix->e->fused_run(2, na, q2.data(), nullptr, ef_search, limit, (uint32_t)g.entry, g.level[g.entry],
                                        i2.data(), d2.data(), c2.data(), st2.data(), cnts, &it2, nullptr, 8))) return ix->fail(rc, ix->e->err);
             ix->counters[4] += cnts[0];
@@ -2687,13 +2736,13 @@ static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, 
     } else {
         for (uint32_t q = 0; q < nq; q++) todo.push_back(q);
     }
-    return lockstep_scan(ix, todo, 0, ef_search, mode, max_scan_tuples, limit, filter, n_filter, tids_out, dist_out, elems_out, counts_out);
+    return lockstep_scan(ix, todo, 0, ef_search, mode, max_scan_tuples, limit, w, tids_out, dist_out, elems_out, counts_out);
 }
 
 int hx_index_search(hx_index *ix, uint32_t nq, uint32_t ef_search, uint32_t k,
                     int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
 {
-    return search_impl(ix, nq, ef_search, 0, 0, k, nullptr, 0, tids_out, dist_out, elems_out, counts_out);
+    return search_impl(ix, nq, ef_search, 0, 0, k, ScanWhere(), tids_out, dist_out, elems_out, counts_out);
 }
 
 int hx_index_search_submit(hx_index *ix, uint32_t slot, uint32_t first_query, uint32_t nq, uint32_t ef_search, uint32_t k)
@@ -2742,7 +2791,7 @@ int hx_index_search_wait(hx_index *ix, uint32_t slot, int64_t *tids_out, float *
     ix->fused_tasks += ss.nq; ix->fused_redo += todo.size();
     if (todo.empty()) return HX_OK;
     // a query that outgrew even the roomy tables: the lock-step driver (still on the GPU kernels) serves it from its engine query slot
-    return lockstep_scan(ix, todo, ss.first, ss.ef, 0, 0, ss.k, nullptr, 0, tids_out, dist_out, elems_out, counts_out);
+    return lockstep_scan(ix, todo, ss.first, ss.ef, 0, 0, ss.k, ScanWhere(), tids_out, dist_out, elems_out, counts_out);
 }
 
 int hx_index_search_iterative(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, int64_t max_scan_tuples,
@@ -2751,7 +2800,48 @@ int hx_index_search_iterative(hx_index *ix, uint32_t nq, uint32_t ef_search, int
 {
     if (mode != 1 && mode != 2) return ix ? ix->fail(HX_E_ARG, "mode must be 1 (relaxed_order) or 2 (strict_order)") : HX_E_ARG;
     if (max_scan_tuples < 1) return ix->fail(HX_E_ARG, "hnsw.max_scan_tuples must be at least 1");
-    return search_impl(ix, nq, ef_search, mode, max_scan_tuples, limit, filter_pass, n_filter, tids_out, dist_out, nullptr, counts_out);
+    // one shared filter, no predicate: the special case of hx_index_search_filtered
+    ScanWhere w; std::vector<int32_t> all0;
+    if (filter_pass) { all0.assign(nq, 0); w.n_filters = 1; w.filters = &filter_pass; w.filter_len = &n_filter; w.filter_of = all0.data(); }
+    return search_impl(ix, nq, ef_search, mode, max_scan_tuples, limit, w, tids_out, dist_out, nullptr, counts_out);
+}
+
+int hx_index_search_filtered(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
+                             uint32_t n_filters, const uint8_t *const *filters, const uint64_t *filter_len, const int32_t *filter_of,
+                             int cmp, const double *radius, int flags,
+                             int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
+{
+    if (!ix) return HX_E_ARG;
+    if (mode != 1 && mode != 2) return ix->fail(HX_E_ARG, "mode must be 1 (relaxed_order) or 2 (strict_order)");
+    if (max_scan_tuples < 1) return ix->fail(HX_E_ARG, "hnsw.max_scan_tuples must be at least 1");
+    if (n_filters > HX_SCAN_MAX_FILTERS) return ix->fail(HX_E_ARG, "more than HX_SCAN_MAX_FILTERS filters");
+    if (n_filters && (!filters || !filter_len)) return ix->fail(HX_E_ARG, "NULL filter table");
+    for (uint32_t f = 0; f < n_filters; f++) if (!filters[f] && filter_len[f]) return ix->fail(HX_E_ARG, "NULL filter");
+    if (filter_of) for (uint32_t q = 0; q < nq; q++) if (filter_of[q] < -1 || filter_of[q] >= (int32_t)n_filters) return ix->fail(HX_E_ARG, "filter_of entry outside [-1, n_filters)");
+    if (cmp != -1 && (cmp < HX_CMP_LT || cmp > HX_CMP_GE)) return ix->fail(HX_E_ARG, "cmp must be -1 or one of HX_CMP_*");
+    if (cmp != -1 && !radius) return ix->fail(HX_E_ARG, "a distance predicate needs radius[nq]");
+    if (flags & ~HX_SCAN_STOP_PAST_RADIUS) return ix->fail(HX_E_ARG, "unknown flag");
+    if ((flags & HX_SCAN_STOP_PAST_RADIUS) && !(mode == 2 && (cmp == HX_CMP_LT || cmp == HX_CMP_LE)))
+        return ix->fail(HX_E_ARG, "HX_SCAN_STOP_PAST_RADIUS needs strict_order and a < or <= predicate");
+    if (cmp != -1 && ix->e->metric == HX_JACCARD) return ix->fail(HX_E_ARG, "no distance predicate on a Jaccard index: its f32 distance is a rounding of the operator's float8 value");
+    if (!tids_out || !counts_out) return ix->fail(HX_E_ARG, "NULL argument");
+    ScanWhere w; w.n_filters = n_filters; w.filters = filters; w.filter_len = filter_len; w.filter_of = filter_of;
+    std::vector<uint64_t> keys; std::vector<uint32_t> keys32;
+    if (cmp != -1) {   // `value <cmp> radius` under float8 comparison as one interval of order keys, as hx_exact_range does it
+        keys.resize(2 * (size_t)nq); keys32.resize(2 * (size_t)nq);
+        const bool root = ix->e->metric == HX_L2SQ;
+        for (uint32_t q = 0; q < nq; q++) {
+            const uint64_t rk = hx_order_key(radius[q]); uint64_t lo = 0, hi = ~0ull;
+            if (cmp == HX_CMP_LT) { if (rk == 0) { lo = ~0ull; hi = 0; } else hi = rk - 1; }
+            else if (cmp == HX_CMP_LE) hi = rk;
+            else if (cmp == HX_CMP_GT) { if (rk == ~0ull) { lo = ~0ull; hi = 0; } else lo = rk + 1; }
+            else lo = rk;
+            keys[2 * (size_t)q] = lo; keys[2 * (size_t)q + 1] = hi;
+            where_keys32(lo, hi, root, &keys32[2 * (size_t)q]);
+        }
+        w.keys = keys.data(); w.keys32 = keys32.data(); w.val_sqrt = root; w.stop_past = (flags & HX_SCAN_STOP_PAST_RADIUS) != 0;
+    }
+    return search_impl(ix, nq, ef_search, mode, max_scan_tuples, limit, w, tids_out, dist_out, elems_out, counts_out);
 }
 
 // A NULL order-by value (`ORDER BY val <-> NULL`): load_element reports distance 0.0 for every element without calling the distance procedure

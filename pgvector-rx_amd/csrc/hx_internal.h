@@ -41,9 +41,32 @@ struct HxKernelStat { uint64_t launches = 0, units = 0; double ms = 0.0; };
 // arguments of an iterative scan on the device (k_fused MODE 2)
 struct HxFusedIter {
     int iter_mode = 1; long long max_tuples = 0;       // 1 relaxed_order, 2 strict_order; hnsw.max_scan_tuples
-    const uint16_t *emask = nullptr; uint64_t n_elems = 0;   // per element: bits 0-9 heap TIDs that pass the filter, bits 12-15 number of heap TIDs
+    const uint16_t *emask = nullptr; uint64_t n_elems = 0;   // mask table, mask_rows rows of n_elems; per element: bits 0-9 heap TIDs that pass the row's filter, bits 12-15 number of heap TIDs
+    uint32_t mask_rows = 1;
     uint32_t *out_tix = nullptr;                       // [ntasks][limit]: which heap TID of out_ids' element
+    // per-query filter and distance predicate (hx_index_search_filtered); host arrays of ntasks entries
+    const uint32_t *t_frow = nullptr;                  // the task's row of the mask table (nullptr: row 0 for all)
+    const uint32_t *t_key = nullptr;                   // {lo, hi} per task: the tuple passes when lo <= hx_order_key32(d, val_sqrt) <= hi (nullptr: no predicate)
+    bool val_sqrt = false;                             // the operator's value is sqrt((double)d) (`<->` on an HX_L2SQ index), else (double)d
+    bool stop_past = false;                            // HX_SCAN_STOP_PAST_RADIUS
 };
+// float8 order as an integer order (PostgreSQL's float8 comparison: -0.0 == +0.0, every NaN equal and above everything); hx_exact_core.h's ex_key
+__host__ __device__ __forceinline__ uint64_t hx_order_key(double d)
+{
+    if (d != d) return ~0ull;
+    if (d == 0.0) return 0x8000000000000000ull;
+    const uint64_t b = __builtin_bit_cast(uint64_t, d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// The same for an f32 distance d whose operator value is (double)d, or sqrt((double)d) with `root`: a negative d then has the value NaN.  The value is
+// monotone in this key and NaN exactly at ~0, so a float8 predicate on the value is an interval of these keys.
+__host__ __device__ __forceinline__ uint32_t hx_order_key32(float d, bool root)
+{
+    if (d != d || (root && d < 0.0f)) return ~0u;
+    if (d == 0.0f) return 0x80000000u;
+    const uint32_t b = __builtin_bit_cast(uint32_t, d);
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
 // zero-copy view of a fused launch's results in its pinned staging buffer (valid until the next launch on the same HxFusedIo)
 struct HxFusedView { const uint32_t *ids = nullptr, *cnt = nullptr, *status = nullptr; const float *d = nullptr; };
 struct HxFusedDev;
