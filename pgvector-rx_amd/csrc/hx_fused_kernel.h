@@ -563,7 +563,7 @@ __device__ __forceinline__ void f_worker(KParams &p_in, uint8_t *lds, const uint
                     // emit from the back (scan.rs:796-815, 860-874); the elements' TID masks are fetched 64 at a time
                     uint32_t left = wl;
                     // The query's WHERE clause: its row of the mask table and the interval of f32 order keys its distance predicate comes to (the host
-                    // maps `value <cmp> radius` onto the returned f32, hx_index.cpp: where_keys32).  Fetched per emit phase into scalar registers
+                    // maps `value <cmp> radius` onto the returned f32, hx_internal.h: hx_where_keys32).  Fetched per emit phase into scalar registers
                     // (every lane holds the same task) through a fresh view of the parameters, so nothing of them is live across the search above.
                     KParams &pw = f_params_here(p);
                     const uint32_t tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);

@@ -2520,28 +2520,12 @@ int hx_index_counters(const hx_index *ix, uint64_t counters_out[8])
 // the scans `todo` (indices into the caller's output arrays; engine query slot = q0 + index) on the lock-step host driver
 // The WHERE clause of each query of an iterative scan (hx_index_search_filtered): query q is filtered by filters[filter_of[q]] (-1 / no
 // filter_of: every TID passes) and by keys[2q] <= hx_order_key(value) <= keys[2q + 1] (no keys: no predicate).  keys32: the same predicate as an
-// interval of the returned f32's order keys (where_keys32), which is what the traversal kernel tests; the lock-step driver evaluates the value itself.
+// interval of the returned f32's order keys (hx_where_keys32), which is what the traversal kernel tests; the lock-step driver evaluates the value itself.
 struct ScanWhere {
     uint32_t n_filters = 0; const uint8_t *const *filters = nullptr; const uint64_t *filter_len = nullptr; const int32_t *filter_of = nullptr;
     const uint64_t *keys = nullptr; const uint32_t *keys32 = nullptr; bool val_sqrt = false, stop_past = false;
     int fidx(uint32_t q) const { return (n_filters && filter_of) ? filter_of[q] : -1; }
 };
-
-// The f32 distances whose operator value lies in the key interval [lo, hi]: K(k) = hx_order_key(value of the f32 with order key k) never decreases
-// over k (hx_order_key32: the value is (double)d or sqrt((double)d), both monotone in d, and every d without a value is at the top key), so they
-// are the f32 keys from the first k with K(k) >= lo to the last with K(k) <= hi -- two binary searches.  Empty: {~0, 0}.
-static void where_keys32(uint64_t lo, uint64_t hi, bool root, uint32_t out[2])
-{
-    auto K = [&](uint64_t k) -> uint64_t {
-        const uint32_t b = (k >> 31) ? (uint32_t)k ^ 0x80000000u : ~(uint32_t)k;
-        const float d = __builtin_bit_cast(float, b);
-        return hx_order_key32(d, root) == ~0u ? ~0ull : hx_order_key(root ? std::sqrt((double)d) : (double)d);
-    };
-    const uint64_t kmin = root ? 0x80000000ull : 0x007FFFFFull, kend = 0x100000000ull;     // from 0 (root) / -inf; kend: one past the NaN key
-    auto first_where = [&](auto pred) { uint64_t a = kmin, b = kend; while (a < b) { const uint64_t m = (a + b) >> 1; if (pred(K(m))) b = m; else a = m + 1; } return a; };
-    const uint64_t l = first_where([&](uint64_t v) { return v >= lo; }), h = first_where([&](uint64_t v) { return v > hi; });
-    if (l >= h) { out[0] = ~0u; out[1] = 0u; } else { out[0] = (uint32_t)l; out[1] = (uint32_t)(h - 1); }
-}
 
 static int lockstep_scan(hx_index *ix, const std::vector<uint32_t> &todo, uint32_t q0, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
                          const ScanWhere &w, int64_t *tids_out, float *dist_out, uint32_t *elems_out, uint32_t *counts_out)
@@ -2831,13 +2815,9 @@ int hx_index_search_filtered(hx_index *ix, uint32_t nq, uint32_t ef_search, int 
         keys.resize(2 * (size_t)nq); keys32.resize(2 * (size_t)nq);
         const bool root = ix->e->metric == HX_L2SQ;
         for (uint32_t q = 0; q < nq; q++) {
-            const uint64_t rk = hx_order_key(radius[q]); uint64_t lo = 0, hi = ~0ull;
-            if (cmp == HX_CMP_LT) { if (rk == 0) { lo = ~0ull; hi = 0; } else hi = rk - 1; }
-            else if (cmp == HX_CMP_LE) hi = rk;
-            else if (cmp == HX_CMP_GT) { if (rk == ~0ull) { lo = ~0ull; hi = 0; } else lo = rk + 1; }
-            else lo = rk;
+            uint64_t lo, hi; hx_where_keys(cmp, radius[q], &lo, &hi);
             keys[2 * (size_t)q] = lo; keys[2 * (size_t)q + 1] = hi;
-            where_keys32(lo, hi, root, &keys32[2 * (size_t)q]);
+            hx_where_keys32(lo, hi, root, &keys32[2 * (size_t)q]);
         }
         w.keys = keys.data(); w.keys32 = keys32.data(); w.val_sqrt = root; w.stop_past = (flags & HX_SCAN_STOP_PAST_RADIUS) != 0;
     }

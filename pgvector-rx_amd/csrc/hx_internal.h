@@ -2,6 +2,7 @@
 // Not part of the ABI; the ABI is include/hnswrx.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -66,6 +67,34 @@ __host__ __device__ __forceinline__ uint32_t hx_order_key32(float d, bool root)
     if (d == 0.0f) return 0x80000000u;
     const uint32_t b = __builtin_bit_cast(uint32_t, d);
     return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+// `value <cmp> radius` (HX_CMP_*) under float8 comparison as one interval [lo, hi] of hx_order_key; empty as [~0, 0].  Shared by hx_exact_range and
+// hx_index_search_filtered; host-only, tests/test_where_keys_host.py checks it against the comparison itself.
+inline void hx_where_keys(int cmp, double radius, uint64_t *lo, uint64_t *hi)
+{
+    const uint64_t rk = hx_order_key(radius);
+    *lo = 0; *hi = ~0ull;
+    if (cmp == HX_CMP_LT) { if (rk == 0) { *lo = ~0ull; *hi = 0; } else *hi = rk - 1; }
+    else if (cmp == HX_CMP_LE) *hi = rk;
+    else if (cmp == HX_CMP_GT) { if (rk == ~0ull) { *lo = ~0ull; *hi = 0; } else *lo = rk + 1; }
+    else *lo = rk;
+}
+// K(k) = hx_order_key(value of the f32 with order key k); never decreases over k
+inline uint64_t hx_where_value_key(uint64_t k, bool root)
+{
+    const uint32_t b = (k >> 31) ? (uint32_t)k ^ 0x80000000u : ~(uint32_t)k;
+    const float d = __builtin_bit_cast(float, b);
+    return hx_order_key32(d, root) == ~0u ? ~0ull : hx_order_key(root ? std::sqrt((double)d) : (double)d);
+}
+// The f32 distances whose operator value lies in the key interval [lo, hi]: K never decreases over k (hx_order_key32: the value is (double)d or
+// sqrt((double)d), both monotone in d, and every d without a value is at the top key), so they are the f32 keys from the first k with K(k) >= lo to
+// the last with K(k) <= hi -- two binary searches.  Empty: {~0, 0}.
+inline void hx_where_keys32(uint64_t lo, uint64_t hi, bool root, uint32_t out[2])
+{
+    const uint64_t kmin = root ? 0x80000000ull : 0x007FFFFFull, kend = 0x100000000ull;     // from 0 (root) / -inf; kend: one past the NaN key
+    auto first_where = [&](auto pred) { uint64_t a = kmin, b = kend; while (a < b) { const uint64_t m = (a + b) >> 1; if (pred(hx_where_value_key(m, root))) b = m; else a = m + 1; } return a; };
+    const uint64_t l = first_where([&](uint64_t v) { return v >= lo; }), h = first_where([&](uint64_t v) { return v > hi; });
+    if (l >= h) { out[0] = ~0u; out[1] = 0u; } else { out[0] = (uint32_t)l; out[1] = (uint32_t)(h - 1); }
 }
 // zero-copy view of a fused launch's results in its pinned staging buffer (valid until the next launch on the same HxFusedIo)
 struct HxFusedView { const uint32_t *ids = nullptr, *cnt = nullptr, *status = nullptr; const float *d = nullptr; };

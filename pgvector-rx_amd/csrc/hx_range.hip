@@ -315,17 +315,6 @@ hipError_t rg_scan(hx_engine *e, int op, const RgArgs &a, uint32_t Q, uint32_t t
     }
 }
 
-// the keys of `value <cmp> radius` as one interval [lo, hi]; empty as [~0, 0]
-void rg_interval(int cmp, double radius, uint64_t *lo, uint64_t *hi)
-{
-    const uint64_t rk = ex_key(radius);
-    *lo = 0; *hi = ~0ull;
-    if (cmp == HX_CMP_LT) { if (rk == 0) { *lo = ~0ull; *hi = 0; } else *hi = rk - 1; }
-    else if (cmp == HX_CMP_LE) *hi = rk;
-    else if (cmp == HX_CMP_GT) { if (rk == ~0ull) { *lo = ~0ull; *hi = 0; } else *lo = rk + 1; }
-    else *lo = rk;
-}
-
 } // namespace
 
 // =================================================================================================
@@ -463,7 +452,7 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
     const int neg_zero = op == HX_OP_NEG_IP;
     for (uint32_t q0 = 0; q0 < nq; q0 += nqb) {
         const uint32_t nb = std::min(nqb, nq - q0), tiles = (nb + Q - 1) / Q;
-        for (uint32_t i = 0; i < nb; i++) rg_interval(cmp, radius[q0 + i], &klo[i], &khi[i]);
+        for (uint32_t i = 0; i < nb; i++) hx_where_keys(cmp, radius[q0 + i], &klo[i], &khi[i]);
         HX_HIP(e, hipMemcpyAsync(d + o_klo, klo.data(), (size_t)nb * 8, hipMemcpyHostToDevice, e->stream));
         HX_HIP(e, hipMemcpyAsync(d + o_khi, khi.data(), (size_t)nb * 8, hipMemcpyHostToDevice, e->stream));
         // pass 1: counts, and the hits that fit their segment's staging

@@ -44,7 +44,13 @@ def random_sparse(rng, n, dim, max_nnz):
     return rows
 
 
-def make_rows(dt, n, dim, rng):
+def make_rows(dt, n, dim, rng, data="uniform"):
+    if data != "uniform":                                      # signed rows: N(0, 1); "scaled": times a per-row factor 10**U(-3, 3)
+        x = rng.standard_normal((n, dim))
+        if data == "scaled":
+            x = x * 10.0 ** rng.uniform(-3.0, 3.0, (n, 1))
+        x = x.astype(np.float32)
+        return x if dt == hx.F32 else x.astype(np.float16).view(np.uint16)
     if dt == hx.F32:
         return rng.random((n, dim)).astype(np.float32)
     if dt == hx.F16:
@@ -57,17 +63,13 @@ def make_rows(dt, n, dim, rng):
 class Setup:
     """A device index and the oracle's index on the same rows (heap TID == row id), NQ queries uploaded."""
 
-    def __init__(self, dt, metric, dim, n, seed=7):
+    def __init__(self, dt, metric, dim, n, seed=7, data="uniform", precheck=None):
         rng = np.random.default_rng(seed)
         m, efc = 8, 32
         self.dt, self.metric, self.n = dt, metric, n
-        rows = make_rows(dt, n, dim, rng)
+        rows = make_rows(dt, n, dim, rng, data)
         levels = hx.draw_levels(n, m, seed=seed)
-        self.e = hx.Engine(dt, metric, dim, n)
-        self.e.append(rows)
-        self.ix = hx.Index(self.e, m, efc)
         batch = 1 if dt == hx.SPARSE else 64
-        self.ix.insert(0, levels, batch=batch)
         # the summation order of the existing iterative parity tests (test_iterative_scan_on_device_equals_lockstep_and_oracle; sparsevec: test_gpu_sparse)
         self.o = orc.Index(dt, metric, dim, m=m, ef_construction=efc) if dt == hx.SPARSE else orc.Index(dt, metric, dim, m=m, ef_construction=efc, order=orc.W64)
         tids = np.arange(n, dtype=np.int64)
@@ -75,13 +77,19 @@ class Setup:
         for b in hx.batch_schedule(0, n, batch):
             self.o.insert_batch(rows[i:i + b], levels[i:i + b], tids[i:i + b])
             i += b
-        self.qs = make_rows(dt, NQ, dim, rng)
+        self.qs = make_rows(dt, NQ, dim, rng, data)
+        self._streams = {}
+        self._near = [self.o.bruteforce_topk(self.qs[q], 500)[1] for q in range(NQ)]
+        if precheck is not None:
+            precheck(self)                                      # what the data is meant to do, on the oracle alone: no device call so far
+        self.e = hx.Engine(dt, metric, dim, n)
+        self.e.append(rows)
+        self.ix = hx.Index(self.e, m, efc)
+        self.ix.insert(0, levels, batch=batch)
         self.e.set_queries(self.qs)
         t = np.arange(n)
         self.filters = [(t % 100 == 0).astype(np.uint8), (t % 10 == 0).astype(np.uint8), (t % 2 == 0).astype(np.uint8), (t % 10 == 3).astype(np.uint8)]   # 1 %, 10 %, 50 %, 10 %
         self.filter_of = np.array([(q % 5) - 1 for q in range(NQ)], np.int32)                    # -1 (no filter), 0, 1, 2, 3
-        self._streams = {}
-        self._near = [self.o.bruteforce_topk(self.qs[q], 500)[1] for q in range(NQ)]
 
     def stream(self, q, mode, max_tuples=20000):
         key = (q, mode, max_tuples)
@@ -101,6 +109,44 @@ class Setup:
                 r[q] = -np.inf
             else:
                 r[q] = op_value(self.metric, self._near[q][{0: 4, 1: 49, 2: 499, 5: 4}[kind]])
+        return r
+
+    def values(self, q, mode=2):
+        """The distinct operator values of the query's stream, ascending (NaN left out)."""
+        v = np.unique(np.array([op_value(self.metric, d) for _, d, _ in self.stream(q, mode)], np.float64))
+        return v[~np.isnan(v)]
+
+    def edge_radii(self):
+        """Per query, radii that are NOT values of its stream: +0.0, -0.0, +inf; the float8 midpoint between its 5th and 6th distinct values (`<` and `<=`
+        then select the same tuples); for <->, the float8 neighbours of sqrt(d5) on both sides; for <#>, radii of the sign opposite to most of the stream
+        (the nearest tuples of an inner-product scan are negative); its own 5th value (the tie); NaN."""
+        r = np.empty(NQ, np.float64)
+        for q in range(NQ):
+            v, kind = self.values(q), q % 9
+            if kind == 0:
+                r[q] = 0.0
+            elif kind == 1:
+                r[q] = -0.0
+            elif kind == 2:
+                r[q] = np.inf
+            elif kind == 3:
+                r[q] = (v[4] + v[5]) / 2
+                assert v[4] < r[q] < v[5]
+            elif kind in (4, 5):
+                up = kind == 4
+                if self.metric == hx.L2SQ:
+                    r[q] = np.nextafter(v[4], np.inf if up else -np.inf)
+                elif self.metric == hx.NEG_IP:
+                    pos = v[v > 0]
+                    r[q] = (pos[0] + pos[1]) / 2 if up else float(np.float32(pos[len(pos) // 2]))
+                else:
+                    r[q] = np.nextafter(v[4], np.inf if up else -np.inf)
+            elif kind == 6:
+                r[q] = v[4]
+            elif kind == 7:
+                r[q] = np.nan
+            else:
+                r[q] = -1.5 if self.metric != hx.NEG_IP else (v[9] + v[10]) / 2        # a negative radius
         return r
 
     def expected(self, q, mode, cmp, radius, limit=LIMIT, max_tuples=20000, filtered=True):
@@ -123,6 +169,25 @@ class Setup:
 
 def same(a, b):
     return np.array_equal(a[3], b[3]) and np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and np.array_equal(a[2], b[2])
+
+
+SIGNED = [(hx.F32, hx.NEG_IP, 24, 4000, "normal"), (hx.F32, hx.L1, 12, 4000, "normal"), (hx.F16, hx.NEG_IP, 40, 4000, "normal"), (hx.F32, hx.L2SQ, 8, 4000, "scaled")]
+SIGNED_IDS = ["vector-ip-normal", "vector-l1-normal", "halfvec-ip-normal", "vector-l2-scaled"]
+
+
+def signed_precheck(s):
+    """On the oracle's streams alone: <#> streams hold both signs for at least a quarter of the queries, and some query has a value of exactly +-0 or
+    values on both sides of its zero radius; every kind of row has coordinates of both signs."""
+    if s.metric != hx.NEG_IP:
+        return
+    both = zero = 0
+    for q in range(NQ):
+        for mode in (1, 2):
+            v = s.values(q, mode)
+            both += mode == 2 and (v < 0).any() and (v > 0).any()
+            zero += (v == 0).any() or (q % 9 in (0, 1) and (v < 0).any() and (v > 0).any())
+    print("streams with both signs", both, "of", NQ, "; zero values or crossings of a zero radius", zero)
+    assert 4 * both >= NQ and zero > 0
 
 
 SHAPES = [(hx.F32, hx.L2SQ, 8, 6000), (hx.F16, hx.NEG_IP, 24, 4000), (hx.BIT, hx.HAMMING, 64, 5000), (hx.SPARSE, hx.L2SQ, 300, 1200)]
@@ -162,6 +227,86 @@ def test_filtered_scan_equals_the_oracle_stream_filtered_as_the_executor_would(d
             if q % 6 in (0, 1, 2, 5):
                 ties += any(op_value(metric, d) == radius[q] for _, d, _ in s.stream(q, mode))
     assert ties > 0
+    s.close()
+
+
+@pytest.mark.parametrize("dt,metric,dim,n,data", SIGNED, ids=SIGNED_IDS)
+def test_filtered_scan_on_signed_rows_equals_the_oracle_stream_filtered_as_the_executor_would(dt, metric, dim, n, data):
+    """N(0, 1) rows and queries (<-> : rows scaled per row over six decades): distances of both signs, and radii that are no value of the stream (edge_radii)
+    next to the stored-value, NaN and -inf kinds.  TIDs, counts and distance bits are the oracle's stream filtered in Python by f8cmp on op_value, on the
+    traversal kernel (redone == 0), on the lock-step driver, and through one single-mask call of hx_index_search_iterative per query."""
+    s = Setup(dt, metric, dim, n, seed=7, data=data, precheck=signed_precheck)
+    all_rows = np.arange(n, dtype=np.uint32)
+    for radius in (s.edge_radii(), s.radii()):
+        for mode in (1, 2):
+            res = {}
+            for cmp in (hx.CMP_LT, hx.CMP_LE, hx.CMP_GT, hx.CMP_GE):
+                s.e.set_queries(s.qs)
+                before = s.ix.fused_stats()
+                got = s.ix.search_filtered(NQ, EFS, mode, 20000, LIMIT, filters=s.filters, filter_of=s.filter_of, cmp=cmp, radius=radius)
+                after = s.ix.fused_stats()
+                assert after["tasks"] == before["tasks"] + NQ and after["redone"] == before["redone"]
+                res[cmp] = got
+                for q in range(NQ):
+                    want = s.expected(q, mode, cmp, radius)
+                    c = int(got[3][q])
+                    print("shape", dt, metric, "mode", mode, "cmp", cmp, "q", q, "radius", radius[q], "count", c, "want", len(want))
+                    assert c == len(want), (mode, cmp, q, radius[q])
+                    assert got[0][q, :c].tolist() == [t for t, _ in want], (mode, cmp, q, radius[q])
+                    assert np.array_equal(got[1][q, :c].view(np.uint32), np.array([d for _, d in want], np.float32).view(np.uint32)), (mode, cmp, q)
+                s.ix.set_fused(False)
+                try:
+                    ls = s.ix.search_filtered(NQ, EFS, mode, 20000, LIMIT, filters=s.filters, filter_of=s.filter_of, cmp=cmp, radius=radius)
+                finally:
+                    s.ix.set_fused(True)
+                assert same(got, ls), (mode, cmp)
+                if (mode, cmp) in [(2, hx.CMP_LT), (1, hx.CMP_GE)]:                                        # the one-mask-per-query call of the existing entry point
+                    for q in range(0, NQ, 2):
+                        val = op_value(metric, s.e.distances(s.qs[q], all_rows))
+                        mask = np.array([f8cmp(v, CMPS[cmp], radius[q]) for v in val], np.uint8)
+                        if s.filter_of[q] >= 0:
+                            mask &= s.filters[s.filter_of[q]]
+                        s.e.set_queries(s.qs[q:q + 1])
+                        t1, d1, c1 = s.ix.search_iterative(1, EFS, mode, 20000, LIMIT, mask)
+                        assert int(got[3][q]) == int(c1[0]), (mode, cmp, q)
+                        assert np.array_equal(got[0][q], t1[0]) and np.array_equal(got[1][q].view(np.uint32), d1[0].view(np.uint32)), (mode, cmp, q)
+                    s.e.set_queries(s.qs)
+            for q in range(NQ):                                                                            # a radius between two values: < and <= agree, > and >= agree
+                if True:
+                    if not any(op_value(metric, d) == radius[q] for _, d, _ in s.stream(q, mode)) and not np.isnan(radius[q]):
+                        for a, b in ((hx.CMP_LT, hx.CMP_LE), (hx.CMP_GT, hx.CMP_GE)):
+                            assert res[a][3][q] == res[b][3][q] and np.array_equal(res[a][0][q], res[b][0][q]), (mode, q, radius[q])
+    s.close()
+
+
+def test_stop_past_radius_on_a_signed_inner_product_stream():
+    """HX_SCAN_STOP_PAST_RADIUS, strict order, `<` and `<=`, on N(0, 1) rows under <#>: radii that are negative (the 20th-nearest value), zero (+0.0 and -0.0)
+    and positive (three quarters down the stream), every one inside the stream.  The tuples are those without the flag and the oracle's; the scan's distance
+    evaluations (hx_index_counters()[4]) are strictly fewer with it."""
+    s = Setup(hx.F32, hx.NEG_IP, 24, 4000, seed=7, data="normal", precheck=signed_precheck)
+    n = s.n
+    vals = [s.values(q) for q in range(NQ)]
+    for name, radius, limit in [("negative", np.array([v[19] for v in vals]), 100), ("+0", np.zeros(NQ), n), ("-0", -np.zeros(NQ), n),
+                                ("positive", np.array([v[3 * len(v) // 4] for v in vals]), n)]:
+        for q in range(NQ):
+            assert vals[q][0] < radius[q] < vals[q][-1] or (radius[q] == 0 and vals[q][0] < 0 < vals[q][-1])   # inside the stream
+        assert (np.sign(radius) == {"negative": -1, "+0": 0, "-0": 0, "positive": 1}[name]).all()
+        for cmp in (hx.CMP_LT, hx.CMP_LE):
+            for fused in ((True, False) if limit == 100 else (True,)):                                     # the lock-step driver: the short scans
+                s.ix.set_fused(fused)
+                c0 = int(s.ix.counters()[4])
+                plain = s.ix.search_filtered(NQ, EFS, 2, 20000, limit, cmp=cmp, radius=radius)
+                c1 = int(s.ix.counters()[4])
+                flag = s.ix.search_filtered(NQ, EFS, 2, 20000, limit, cmp=cmp, radius=radius, stop_past_radius=True)
+                c2 = int(s.ix.counters()[4])
+                print("radius", name, "cmp", cmp, "fused", fused, "distance evaluations without the flag", c1 - c0, "with", c2 - c1, "counts", plain[3][:6].tolist())
+                assert same(plain, flag), (name, cmp, fused)
+                assert (plain[3] < limit).all() and plain[3].sum() > 0
+                assert 0 < c2 - c1 < c1 - c0, (name, cmp, fused)
+                for q in range(0, NQ, 6):
+                    want = s.expected(q, 2, cmp, radius, limit=limit, filtered=False)
+                    assert plain[0][q, :plain[3][q]].tolist() == [t for t, _ in want], (name, cmp, q)
+    s.ix.set_fused(True)
     s.close()
 
 
