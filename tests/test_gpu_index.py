@@ -23,23 +23,39 @@ def make_rows(dtype, n, dim, rng):
     return np.packbits(rng.integers(0, 2, (n, dim)).astype(np.uint8), axis=1, bitorder="big")
 
 
-def build_both(dtype, metric, dim, rows, levels, m, efc, batch, fused=True):
+def build_device(dtype, metric, dim, rows, levels, m, efc, batch, fused=True, mfma=None):
+    """The device half of build_both: engine, index and the element id of every row."""
     n = len(levels)
     e = hx.Engine(dtype, metric, dim, n)
     e.append(rows)
     ix = hx.Index(e, m, efc)
     ix.set_fused(fused)
+    if mfma is not None:
+        ix.set_mfma(mfma)
     elem = ix.insert(0, levels, batch=batch)
+    return e, ix, elem
+
+
+def build_oracle(dtype, metric, dim, rows, levels, m, efc, batch, tombstones=False):
+    """The oracle half of build_both: the oracle's snapshot schedule with the same batch size (batch=1 == the reference's sequential
+    schedule, rows merged as duplicates staying behind as tombstones so ids line up)."""
+    n = len(levels)
     o = orc.Index(dtype, metric, dim, m=m, ef_construction=efc, order=orc.W64)
+    if tombstones:
+        o.set_ondisk_tombstones(True)
     tids = np.arange(n, dtype=np.int64)
-    # the oracle's snapshot schedule with the same batch size (batch=1 == the reference's sequential
-    # schedule, rows merged as duplicates staying behind as tombstones so ids line up)
     oelem = []
     i = 0
     for b in hx.batch_schedule(0, n, batch):
         oelem.append(o.insert_batch(rows[i:i + b], levels[i:i + b], tids[i:i + b]))
         i += b
-    return e, ix, elem, o, np.concatenate(oelem)
+    return o, np.concatenate(oelem)
+
+
+def build_both(dtype, metric, dim, rows, levels, m, efc, batch, fused=True):
+    e, ix, elem = build_device(dtype, metric, dim, rows, levels, m, efc, batch, fused)
+    o, oelem = build_oracle(dtype, metric, dim, rows, levels, m, efc, batch)
+    return e, ix, elem, o, oelem
 
 
 def assert_same_graph(ix, o, n):
@@ -442,12 +458,12 @@ def test_staged_batches_two_rank_simulation(fused):
         e.close()
 
 
-def test_device_batches_two_rank_simulation():
-    """The device-resident exchange of pgvector-rx_amd/dist_build.py played by two engines on one GPU: member records and
-    pruned-list records move between the 'ranks' as device buffers only; both replicas must equal the oracle's graph."""
+def device_batches_two_rank_simulation(efc, n=2500):
+    """Body of test_device_batches_two_rank_simulation for one ef_construction; returns (device batches played, W-table bytes per member seen
+    inside each open device batch)."""
     import torch
     rng = np.random.default_rng(78)
-    n, dim, m, efc, batch, world = 2500, 24, 16, 64, 256, 2
+    dim, m, batch, world = 24, 16, 256, 2
     rows = make_rows(hx.F32, n, dim, rng)
     rows[300] = rows[5]
     rows[1203] = rows[1200]
@@ -460,7 +476,7 @@ def test_device_batches_two_rank_simulation():
         e.append(rows)
         ranks.append((e, hx.Index(e, m, efc)))
     rb, lb = ranks[0][1].dbatch_record_bytes, ranks[0][1].dbatch_list_record_bytes
-    done, n_dev = 0, 0
+    done, n_dev, wtab_bytes = 0, 0, []
     for b in hx.batch_schedule(0, n, batch):
         lv, td = levels[done:done + b], tids[done:done + b]
         if ranks[0][1].entry < 0 or b < 16 or not ranks[0][1].dbatch_supported(lv):
@@ -474,6 +490,7 @@ def test_device_batches_two_rank_simulation():
         torch.cuda.synchronize()                                                 # the engines run on their own streams
         for r, (_, ix) in enumerate(ranks):
             ix.dbatch_begin(done, lv, td)
+            wtab_bytes.append(ix.dbatch_wtab_bytes)
             lo, hi = min(b, r * per), min(b, r * per + per)
             ix.dbatch_search(lo, hi, recs.data_ptr() + lo * rb)                 # "all-gather": both ranks write into the one buffer
         counts = [ix.dbatch_links(r, world, recs.data_ptr()) for r, (_, ix) in enumerate(ranks)]
@@ -489,12 +506,19 @@ def test_device_batches_two_rank_simulation():
                     ix.dbatch_import_links(bufs[s].data_ptr(), counts[s])
             ix.dbatch_end(b)
         done += b
-    assert n_dev >= 5
     for _, ix in ranks:
         assert_same_graph(ix, o, n)
     for e, ix in ranks + [(e0, ix0)]:
         ix.close()
         e.close()
+    return n_dev, wtab_bytes
+
+
+def test_device_batches_two_rank_simulation():
+    """The device-resident exchange of pgvector-rx_amd/dist_build.py played by two engines on one GPU: member records and
+    pruned-list records move between the 'ranks' as device buffers only; both replicas must equal the oracle's graph."""
+    n_dev, _ = device_batches_two_rank_simulation(64)
+    assert n_dev >= 5
 
 
 def test_fused_equals_lockstep_at_scale():
