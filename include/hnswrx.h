@@ -198,7 +198,8 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
  * distances), kind 1 = pair-block kernel (units = pairs), 2 = traversal kernel, 3 = back-link kernels, 4 = MFMA pair kernel (units = pairs),
  * 5 = pipelined scans (hx_index_search_submit): units = distances, ms = the UNION of the overlapping launches' busy intervals,
  * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16),
- * 7 = exact scans (hx_exact_search): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
+ * 7 = exact scans (hx_exact_search, hx_exact_search_filtered): units = distances evaluated (passing rows x nq; with a filter per query the sum
+ *     over the queries of their filter's passing rows), ms = the summed kernel time of the calls,
  * 8 = range scans (hx_exact_range): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
  * 9 = exact re-rank (hx_exact_rerank): units = distances evaluated (candidates listed), ms = the summed kernel time of the calls,
  * 10 = vector -> halfvec casts (hx_append_rows_halfvec, hx_set_queries_halfvec): units = elements cast. */
@@ -240,6 +241,34 @@ enum hx_op { HX_OP_L2 = 0, HX_OP_NEG_IP = 1, HX_OP_COSINE = 2, HX_OP_L1 = 3, HX_
 #define HX_EXACT_MAX_K 1024
 int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
                     const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
+
+/* ---- exact k-NN scan with a WHERE filter per query: a batch of `WHERE tenant = $1 ORDER BY v <op> $2 LIMIT k` in one call ----------------
+ * Definition: the outputs equal, byte for byte, what nq separate hx_exact_search calls would write -- the call for query i with the same op,
+ * row range and k, the one query slot first_query + i, row_pass = filters[filter_of[i]] (NULL where filter_of[i] is -1) and rows i of ids_out,
+ * dist_out and counts_out.  Everything said of hx_exact_search holds through that equality: the operator values in the canonical summation
+ * order, the float8 order with -0.0 == +0.0 and NaN last, ties by ascending row id, the 0xFFFFFFFF / NaN padding past the count, the default
+ * quiet NaN, stray bits past n_rows in a bitmap's last word ignored.  Outputs are in the caller's query order.
+ *   filters[f] : a row_pass bitmap of ceil(n_rows / 64) words.  Filters may overlap, pass no row (count 0 and padding) or fewer than k rows.  A
+ *                filter that no query references may be NULL; it is neither read, uploaded nor compacted.
+ *   filter_of  : nq entries in [-1, n_filters); -1 = every row passes.  NULL = -1 for all.  Queries of one filter need not be adjacent.
+ * HX_E_ARG: everything hx_exact_search rejects, with the same messages, and n_filters > HX_EXACT_MAX_FILTERS (the host splits such batches),
+ * filters NULL with n_filters > 0, a NULL filters[f] that a query references, a filter_of entry outside [-1, n_filters).  The arguments are
+ * checked before a device is touched.  Synchronous on the engine stream; reads only, so it may run beside a pipelined index scan.
+ * One distinct filter (every query names the same one, or none does): the call IS hx_exact_search with that bitmap -- the same path, the same
+ * sidecar decision, the same hx_kernel_stats and hx_exact_sidecar_stats accounting.
+ * Two or more distinct filters: the queries are grouped by filter; ONE launch compacts all referenced bitmaps into row-id lists, one scan launch
+ * per query-tile size present (16 / 4 / 1, so at most three) streams each filter's rows once per query tile -- a row that fails every referenced
+ * filter is never read -- and one launch merges; the launch count does not grow with the number of filters.  This path does not use the 8-bit
+ * sidecar (the values are the same either way) and does not move hx_exact_sidecar_stats.
+ * hx_kernel_stats kind 7: units = the sum over the queries of the rows passing that query's filter, ms = kernel time only (not the uploads),
+ * launches = the kernels launched.
+ * Device memory on the grouped path: one bitmap (n_rows / 8 B) and one row-id list (4 B per passing row) per referenced filter that passes a row,
+ * 40 B of work descriptor per scan workgroup (about 1024 of them), 4 + 24 B per query, and the top-k scratch within HX_EXACT_SCRATCH bytes
+ * (default 256 MiB) as for hx_exact_search: query blocks run in turn, and a query tile gets no more row slices than fit it. */
+#define HX_EXACT_MAX_FILTERS 64
+int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                             uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
+                             uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
 
 /* ---- exact range scan: the sequential-scan plans of `WHERE v <op> q < r` and `WHERE v <op> q < r ORDER BY v <op> q` (no LIMIT) ----------
  * Per query slot first_query + i, every row of

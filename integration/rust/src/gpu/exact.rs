@@ -1,0 +1,49 @@
+//! The sequential-scan plans on the engine: exact k-NN scans over the rows as stored (include/hnswrx.h: hx_exact_search*).
+use std::os::raw::c_int;
+
+use super::ffi::*;
+
+/// The `LIMIT k` rows of one query: engine row ids nearest first with the operator's float8 values.
+pub struct ExactRows {
+    pub ids: Vec<u32>,
+    pub distances: Vec<f64>,
+}
+
+/// `WHERE cond_i ORDER BY v <op> q_i LIMIT k` for the engine's query slots `0..filter_of.len()` over all stored rows, in one call.
+/// `filters[f]`: a row bitmap of `ceil(hx_num_rows / 64)` words; `filter_of[i]`: the filter of query `i`, `None` for no `WHERE`.
+/// The executor batches the pending scans of many backends (one tenant predicate each) and splits batches with more than
+/// `HX_EXACT_MAX_FILTERS` distinct filters.
+pub fn exact_search_filtered_gpu(e: *mut hx_engine, op: c_int, k: u32, filters: &[&[u64]], filter_of: &[Option<usize>]) -> Vec<ExactRows> {
+    assert!(filters.len() <= HX_EXACT_MAX_FILTERS as usize, "split the call: more than HX_EXACT_MAX_FILTERS filters");
+    let nq = filter_of.len();
+    let n_rows = unsafe { hx_num_rows(e) };
+    let words = ((n_rows + 63) / 64) as usize;
+    assert!(filters.iter().all(|f| f.len() >= words), "a filter needs ceil(n_rows / 64) words");
+    let ptrs: Vec<*const u64> = filters.iter().map(|f| f.as_ptr()).collect();
+    let of: Vec<i32> = filter_of
+        .iter()
+        .map(|f| match f {
+            None => -1,
+            Some(f) => {
+                assert!(*f < filters.len(), "filter_of names a filter that is not there");
+                *f as i32
+            }
+        })
+        .collect();
+    let mut ids = vec![0u32; nq * k as usize];
+    let mut dist = vec![0f64; nq * k as usize];
+    let mut counts = vec![0u32; nq];
+    unsafe {
+        ck(
+            e,
+            hx_exact_search_filtered(e, op, 0, nq as u32, 0, n_rows, ptrs.len() as u32, ptrs.as_ptr(), of.as_ptr(), k, ids.as_mut_ptr(),
+                                     dist.as_mut_ptr(), counts.as_mut_ptr()),
+        );
+    }
+    (0..nq)
+        .map(|q| {
+            let (a, b) = (q * k as usize, q * k as usize + counts[q] as usize);
+            ExactRows { ids: ids[a..b].to_vec(), distances: dist[a..b].to_vec() }
+        })
+        .collect()
+}

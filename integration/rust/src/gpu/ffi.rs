@@ -51,6 +51,7 @@ pub const HX_OP_L1: c_int = 3; // <+>
 pub const HX_OP_HAMMING: c_int = 4; // <~>
 pub const HX_OP_JACCARD: c_int = 5; // <%>
 pub const HX_EXACT_MAX_K: u32 = 1024;
+pub const HX_EXACT_MAX_FILTERS: u32 = 64; // filters per hx_exact_search_filtered call
 // hx_cmp: the comparison of a range scan, v <op> q <cmp> radius (hx_exact_range)
 pub const HX_CMP_LT: c_int = 0; // <
 pub const HX_CMP_LE: c_int = 1; // <=
@@ -111,6 +112,10 @@ extern "C" {
     // exact k-NN scan (the sequential-scan plan of ORDER BY v <op> q LIMIT k); op: HX_OP_* above
     pub fn hx_exact_search(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, first_row: u64, n_rows: u64, row_pass: *const u64,
                            k: u32, ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;
+    // exact k-NN scan with a WHERE filter per query (a batch of WHERE tenant = $1 ORDER BY v <op> $2 LIMIT k); filter_of: -1 = no filter
+    pub fn hx_exact_search_filtered(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, first_row: u64, n_rows: u64, n_filters: u32,
+                                    filters: *const *const u64, filter_of: *const i32, k: u32, ids_out: *mut u32, dist_out: *mut f64,
+                                    counts_out: *mut u32) -> c_int;
     // exact range scan (the sequential-scan plans of WHERE v <op> q < r, with or without ORDER BY v <op> q); cmp: HX_CMP_*, order: HX_RANGE_BY_*
     pub fn hx_exact_range(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64, n_rows: u64,
                           row_pass: *const u64, order: c_int, cap: u64, offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64,

@@ -10,6 +10,7 @@ F32, F16, BIT, SPARSE = 0, 1, 2, 3
 L2SQ, NEG_IP, L1, HAMMING, JACCARD = 0, 1, 2, 3, 4
 OP_L2, OP_NEG_IP, OP_COSINE, OP_L1, OP_HAMMING, OP_JACCARD = 0, 1, 2, 3, 4, 5   # hx_op: the SQL operators <-> <#> <=> <+> <~> <%>
 EXACT_MAX_K = 1024
+EXACT_MAX_FILTERS = 64                                 # hx_exact_search_filtered
 CMP_LT, CMP_LE, CMP_GT, CMP_GE = 0, 1, 2, 3           # hx_cmp: v <op> q  <  <=  >  >=  radius
 SCAN_MAX_FILTERS, SCAN_STOP_PAST_RADIUS = 64, 1       # hx_index_search_filtered
 RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap order, or the ORDER BY without LIMIT
@@ -98,6 +99,7 @@ def lib():
         "hx_last_kernel_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "hx_kernel_stats": (i32, [vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), i32]),
         "hx_exact_search": (i32, [vp, i32, u32, u32, u64, u64, vp, u32, vp, vp, vp]),
+        "hx_exact_search_filtered": (i32, [vp, i32, u32, u32, u64, u64, u32, vp, vp, u32, vp, vp, vp]),
         "hx_exact_range": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, vp, i32, u64, vp, vp, vp, vp]),
         "hx_exact_rerank": (i32, [vp, i32, u32, u32, vp, vp, u32, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -375,6 +377,25 @@ class Engine:
         dist = np.empty((nq, k), np.float64)
         cnt = np.empty(nq, np.uint32)
         self._ck(lib().hx_exact_search(self.h, op, first_query, nq, first_row, n_rows, _p(words), k, _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
+
+    def exact_search_filtered(self, op, k, filters, filter_of, first_query=0, nq=None, first_row=0, n_rows=None, packed=False):
+        """hx_exact_search_filtered: exact_search with a row filter per query, in one call.  filters: a list of row_pass masks as exact_search
+        takes them (packed=True: of uint64 word arrays); an entry that no query references may be None.  filter_of: per query the index of its
+        filter, -1 for none (None: -1 for all).  Returns (ids, dist, counts) as exact_search does; row i is what exact_search would return for
+        query i alone with row_pass = filters[filter_of[i]]."""
+        nq = self._nq - first_query if nq is None else nq
+        n_rows = self.num_rows - first_row if n_rows is None else n_rows
+        words = [_row_words(f, n_rows, packed) for f in filters]
+        ptrs = (C.c_void_p * max(1, len(words)))(*[None if w is None else w.ctypes.data for w in words])
+        fo = None if filter_of is None else np.ascontiguousarray(filter_of, dtype=np.int32)
+        if fo is not None and (fo.ndim != 1 or len(fo) != nq):
+            raise ValueError("filter_of needs one entry per query")
+        ids = np.empty((nq, k), np.uint32)
+        dist = np.empty((nq, k), np.float64)
+        cnt = np.empty(nq, np.uint32)
+        self._ck(lib().hx_exact_search_filtered(self.h, op, first_query, nq, first_row, n_rows, len(words), ptrs if words else None, _p(fo), k,
+                                                _p(ids), _p(dist), _p(cnt)))
         return ids, dist, cnt
 
     def exact_rerank(self, op, candidates, k, first_query=0):

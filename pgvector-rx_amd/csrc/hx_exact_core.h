@@ -128,6 +128,43 @@ __device__ __forceinline__ void ex_park(const uint8_t *queries, uint32_t qslot0,
     }
 }
 
+// A value every lane of the workgroup holds, loaded from a table (a slot number, a work descriptor's field), as the scalar it is.  Beyond naming
+// it uniform this ends the address chain the compiler's occupancy heuristic follows: it counts an access whose address derives from a loaded value
+// as indirect, and a kernel with many of those is scheduled for 4 waves per SIMD at most -- 20 to 45 VGPRs more than the same loop needs when
+// its tile and slice come from blockIdx.
+__device__ __forceinline__ uint32_t ex_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t ex_uni(uint64_t v) { return ((uint64_t)ex_uni((uint32_t)(v >> 32)) << 32) | ex_uni((uint32_t)v); }
+
+// ex_park for queries that are not consecutive slots: parks slots[0 .. nlive) (nlive <= Q; the rest of a partial tile re-reads the last one).
+// slots and nlive are uniform over the workgroup.  Same LDS layout, qn[] and barriers as ex_park.
+template <class OP, int HOP, int Q, class INIT>
+__device__ __forceinline__ void ex_park_slots(const uint8_t *queries, const uint32_t *__restrict__ slots, uint32_t nlive, uint32_t pitch, uint32_t cap_sp,
+                                              uint8_t *q_lds, float *qn, INIT &&init)
+{
+    constexpr bool kCos = HOP == HX_OP_COSINE, kSp = OP::kSparse;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (int i = 0; i < Q; i++) {
+        const uint8_t *src = queries + (size_t)ex_uni(slots[(uint32_t)i < nlive ? (uint32_t)i : nlive - 1]) * pitch;
+        for (uint32_t o = threadIdx.x * 16u; o < pitch; o += EX_THREADS * 16u) *(u4 *)(q_lds + o * Q + i * 16) = *(const u4 *)(src + o);
+    }
+    init();
+    __syncthreads();
+    if constexpr (kCos) {
+        for (int i = wave; i < Q; i += EX_WAVES) {
+            float v = 0.0f;
+            if constexpr (kSp) {
+                if (lane == 0) { const SpRow r = sp_row((const uint8_t *)q_lds, cap_sp); for (int t = 0; t < r.nnz; t++) v += r.val[t] * r.val[t]; }
+            } else {
+                typename OP::acc_t acc; OP::init(acc);
+                for (uint32_t c = lane * 16u; c < pitch; c += 1024u) { const u4 x = *(const u4 *)(q_lds + c * Q + i * 16); OP::add(acc, x, x); }
+                v = lanes_sum_f<64>(acc);
+            }
+            if (lane == 0) qn[i] = v;
+        }
+        __syncthreads();
+    }
+}
+
 // Evaluates the RIF row slots rp[0..RIF) of this lane's LPR-lane group against the Q parked queries and calls emit(i, j, value) for query i
 // and slot j, slot-major (j outer, i inner); every lane of the group holds the value.  Sparsevec: LPR == RIF == Q == 1.
 template <class OP, int HOP, int LPR, int RIF, int Q, class EMIT>
