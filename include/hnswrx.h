@@ -200,7 +200,8 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
  * 6 = select_neighbors on the Gram matrices of the matrix-core build path (k_wselect; kind 4 then is its GEMM, k_wgemm_f16),
  * 7 = exact scans (hx_exact_search, hx_exact_search_filtered): units = distances evaluated (passing rows x nq; with a filter per query the sum
  *     over the queries of their filter's passing rows), ms = the summed kernel time of the calls,
- * 8 = range scans (hx_exact_range): units = distances evaluated (passing rows x nq), ms = the summed kernel time of the calls,
+ * 8 = range scans (hx_exact_range, hx_exact_range_filtered): units = distances evaluated (passing rows x nq; with a filter per query the sum
+ *     over the queries of their filter's passing rows), ms = the summed kernel time of the calls,
  * 9 = exact re-rank (hx_exact_rerank): units = distances evaluated (candidates listed), ms = the summed kernel time of the calls,
  * 10 = vector -> halfvec casts (hx_append_rows_halfvec, hx_set_queries_halfvec): units = elements cast. */
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset);
@@ -304,6 +305,44 @@ enum hx_range_order { HX_RANGE_BY_ROW = 0, HX_RANGE_BY_DISTANCE = 1 };
 int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
                    uint64_t first_row, uint64_t n_rows, const uint64_t *row_pass, int order, uint64_t cap,
                    uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
+
+/* ---- exact range scan with a WHERE filter per query: a batch of `WHERE tenant = $1 AND v <op> $2 < r` in one call --------------------------
+ * Definition: the outputs equal, byte for byte, the CSR concatenation of nq separate hx_exact_range calls, one per query in the caller's order --
+ * the call for query i with the same op, cmp, row range and order, the one query slot first_query + i, the one radius radius[i] and
+ * row_pass = filters[filter_of[i]] (NULL where filter_of[i] is -1).  offsets_out[i + 1] - offsets_out[i] is that call's total, ids_out and
+ * dist_out hold the calls' rows one after the other, *total_out is the sum.  Everything said of hx_exact_range holds through that equality: the
+ * operator values of hx_exact_search bit for bit, the float8 predicate with -0.0 == +0.0 and NaN above everything, heap order or float8 order
+ * with ties by row id, the default quiet NaN, stray bits past n_rows in a bitmap's last word ignored.
+ *   filters, filter_of, n_filters: as for hx_exact_search_filtered -- at most HX_EXACT_MAX_FILTERS bitmaps of ceil(n_rows / 64) words; filters may
+ *                overlap, pass no row, or be NULL when no query references them; filter_of NULL = -1 for all; queries of one filter need not be
+ *                adjacent.
+ * Count only (ids_out == NULL && dist_out == NULL), ids without values (dist_out == NULL) and the capacity rule are hx_exact_range's: *total_out
+ * and offsets_out are always the true ones, and the call returns HX_E_NOMEM ("capacity exceeded") when the total exceeds cap.
+ * HX_RANGE_BY_DISTANCE keeps its one exception: a single query whose hits do not fit this call's output window gives HX_E_NOMEM with the counts
+ * filled.  The window's size depends on the call's own metadata, so the byte equality is claimed for calls that succeed on both sides.
+ * HX_E_ARG: everything hx_exact_range rejects, with its messages, and the filter errors of hx_exact_search_filtered, with its messages; all are
+ * checked before a device is touched and before any output is written.
+ * One distinct filter (every query names the same one, or none does): the call IS hx_exact_range with that bitmap -- the same path, the same
+ * sidecar decision, the same accounting.  No referenced filter passes a row: zeros are returned without a scan.
+ * Two or more distinct filters: ONE launch compacts all referenced bitmaps into row-id lists in row order.  Query blocks are consecutive ranges of
+ * the caller's query order; inside a block the queries are grouped by filter, the groups cut into query tiles of 16 / 4 / 1 and the tiles into
+ * row slices in proportion to their filter's passing rows.  A block's first pass is one scan launch per tile size present -- at most five: tiles
+ * of 16 / 4 / 1, and tiles of 4 / 1 through the 8-bit sidecar -- whatever the number of filters; a row that fails every referenced filter is never
+ * read.  Windows, the re-scan of overflowed segments and the sort are hx_exact_range's.
+ * Sidecar: HX_OP_L2 with HX_CMP_LT / HX_CMP_LE on an engine that keeps the sidecar: the tiles of 4 and 1 of a group take it when the group's
+ * passing rows reach hx_exact_range's threshold (65 536; HX_EXACT_SIDECAR = 0 / 1 forces it as there); the outputs are the same bits either way.
+ * It counts into hx_exact_sidecar_stats: code rows = the group's passing rows per tile that took it.
+ * hx_kernel_stats kind 8: units = the sum over the queries of the rows passing that query's filter, ms = kernel time only (not the uploads and
+ * copies), launches = the kernels launched.
+ * Device memory: within HX_RANGE_SCRATCH as for hx_exact_range (a quarter for interval keys, counts and segment bases, 12 B per (query, segment);
+ * a quarter for staging; the rest for the output window and the sort).  Outside it, for the whole call: one bitmap (n_rows / 8 B), its per-word
+ * offsets (n_rows / 16 B) and one row-id list (4 B per passing row) per referenced filter that passes a row, and 32 B of work descriptor per scan
+ * workgroup (about 1024 per block). */
+int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
+                            uint64_t first_row, uint64_t n_rows,
+                            uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
+                            int order, uint64_t cap,
+                            uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
 
 /* ---- exact re-rank of per-query candidate lists: the outer `ORDER BY v <op> q LIMIT k` over a subquery's rows ----------------------------
  * Per query slot first_query + i, the first k rows of

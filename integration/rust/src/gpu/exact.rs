@@ -1,4 +1,5 @@
-//! The sequential-scan plans on the engine: exact k-NN scans over the rows as stored (include/hnswrx.h: hx_exact_search*).
+//! The sequential-scan plans on the engine: exact k-NN and range scans over the rows as stored (include/hnswrx.h: hx_exact_search*,
+//! hx_exact_range*).
 use std::os::raw::c_int;
 
 use super::ffi::*;
@@ -43,6 +44,54 @@ pub fn exact_search_filtered_gpu(e: *mut hx_engine, op: c_int, k: u32, filters: 
     (0..nq)
         .map(|q| {
             let (a, b) = (q * k as usize, q * k as usize + counts[q] as usize);
+            ExactRows { ids: ids[a..b].to_vec(), distances: dist[a..b].to_vec() }
+        })
+        .collect()
+}
+
+/// `WHERE cond_i AND v <op> q_i <cmp> r_i` (`order`: `HX_RANGE_BY_ROW`, or `HX_RANGE_BY_DISTANCE` for `ORDER BY v <op> q_i` without LIMIT) for the
+/// engine's query slots `0..filter_of.len()` over all stored rows, in one call; `filters` and `filter_of` as in `exact_search_filtered_gpu`.
+/// Returns per query its rows and their values.  A first call counts (`SELECT count(*)` stops there), the second is sized to the total.
+pub fn exact_range_filtered_gpu(e: *mut hx_engine, op: c_int, cmp: c_int, radius: &[f64], filters: &[&[u64]], filter_of: &[Option<usize>],
+                                order: c_int) -> Vec<ExactRows> {
+    assert!(filters.len() <= HX_EXACT_MAX_FILTERS as usize, "split the call: more than HX_EXACT_MAX_FILTERS filters");
+    let nq = filter_of.len();
+    assert!(radius.len() == nq, "one radius per query");
+    let n_rows = unsafe { hx_num_rows(e) };
+    let words = ((n_rows + 63) / 64) as usize;
+    assert!(filters.iter().all(|f| f.len() >= words), "a filter needs ceil(n_rows / 64) words");
+    let ptrs: Vec<*const u64> = filters.iter().map(|f| f.as_ptr()).collect();
+    let of: Vec<i32> = filter_of
+        .iter()
+        .map(|f| match f {
+            None => -1,
+            Some(f) => {
+                assert!(*f < filters.len(), "filter_of names a filter that is not there");
+                *f as i32
+            }
+        })
+        .collect();
+    let mut offsets = vec![0u64; nq + 1];
+    let mut total = 0u64;
+    unsafe {
+        ck(
+            e,
+            hx_exact_range_filtered(e, op, cmp, radius.as_ptr(), 0, nq as u32, 0, n_rows, ptrs.len() as u32, ptrs.as_ptr(), of.as_ptr(), order, 0,
+                                    offsets.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), &mut total),
+        );
+    }
+    let mut ids = vec![0u32; total as usize];
+    let mut dist = vec![0f64; total as usize];
+    unsafe {
+        ck(
+            e,
+            hx_exact_range_filtered(e, op, cmp, radius.as_ptr(), 0, nq as u32, 0, n_rows, ptrs.len() as u32, ptrs.as_ptr(), of.as_ptr(), order, total,
+                                    offsets.as_mut_ptr(), ids.as_mut_ptr(), dist.as_mut_ptr(), &mut total),
+        );
+    }
+    (0..nq)
+        .map(|q| {
+            let (a, b) = (offsets[q] as usize, offsets[q + 1] as usize);
             ExactRows { ids: ids[a..b].to_vec(), distances: dist[a..b].to_vec() }
         })
         .collect()

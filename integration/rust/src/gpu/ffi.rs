@@ -120,6 +120,10 @@ extern "C" {
     pub fn hx_exact_range(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64, n_rows: u64,
                           row_pass: *const u64, order: c_int, cap: u64, offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64,
                           total_out: *mut u64) -> c_int;
+    // exact range scan with a WHERE filter per query (a batch of WHERE tenant = $1 AND v <op> $2 < r); filter_of: -1 = no filter
+    pub fn hx_exact_range_filtered(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64,
+                                   n_rows: u64, n_filters: u32, filters: *const *const u64, filter_of: *const i32, order: c_int, cap: u64,
+                                   offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64, total_out: *mut u64) -> c_int;
     // exact re-rank of per-query candidate lists (the outer ORDER BY v <op> q LIMIT k over an index scan's candidates)
     pub fn hx_exact_rerank(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, cand_offsets: *const u64, cand_ids: *const u32, k: u32,
                            ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;

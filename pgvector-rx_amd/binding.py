@@ -101,6 +101,7 @@ def lib():
         "hx_exact_search": (i32, [vp, i32, u32, u32, u64, u64, vp, u32, vp, vp, vp]),
         "hx_exact_search_filtered": (i32, [vp, i32, u32, u32, u64, u64, u32, vp, vp, u32, vp, vp, vp]),
         "hx_exact_range": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, vp, i32, u64, vp, vp, vp, vp]),
+        "hx_exact_range_filtered": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, u32, vp, vp, i32, u64, vp, vp, vp, vp]),
         "hx_exact_rerank": (i32, [vp, i32, u32, u32, vp, vp, u32, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "hx_index_destroy": (i32, [vp]),
@@ -441,6 +442,42 @@ class Engine:
             ids, dist = np.empty(max(n, 1), np.uint32), np.empty(max(n, 1), np.float64)
             rc = L.hx_exact_range(self.h, op, cmp, _p(r), first_query, nq, first_row, n_rows, _p(words), order, n, _p(offsets), _p(ids), _p(dist),
                                   C.byref(total))
+            if rc == E_NOMEM and cap is None and attempt == 0 and total.value > n:
+                n = total.value                              # sized to the total exactly: the second and last call
+                continue
+            self._ck(rc)
+            break
+        t = int(total.value)
+        return offsets, ids[:t], dist[:t]
+
+    def exact_range_filtered(self, op, radius, filters, filter_of, cmp=CMP_LT, first_query=0, nq=None, first_row=0, n_rows=None, packed=False,
+                             ordered=False, count_only=False, cap=None):
+        """hx_exact_range_filtered: exact_range with a row filter per query, in one call.  filters and filter_of as exact_search_filtered takes
+        them; radius: a scalar or one value per query.  Returns what exact_range returns, (offsets, ids, dist) in CSR form: query i's part is
+        what exact_range returns for query i alone with row_pass = filters[filter_of[i]].  cap=None: as in exact_range."""
+        nq = self._nq - first_query if nq is None else nq
+        n_rows = self.num_rows - first_row if n_rows is None else n_rows
+        words = [_row_words(f, n_rows, packed) for f in filters]
+        ptrs = (C.c_void_p * max(1, len(words)))(*[None if w is None else w.ctypes.data for w in words])
+        fo = None if filter_of is None else np.ascontiguousarray(filter_of, dtype=np.int32)
+        if fo is not None and (fo.ndim != 1 or len(fo) != nq):
+            raise ValueError("filter_of needs one entry per query")
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (nq,)))
+        offsets = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64()
+        order = RANGE_BY_DISTANCE if ordered else RANGE_BY_ROW
+        L = lib()
+
+        def call(n, ids, dist):
+            return L.hx_exact_range_filtered(self.h, op, cmp, _p(r), first_query, nq, first_row, n_rows, len(words), ptrs if words else None, _p(fo),
+                                             order, n, _p(offsets), _p(ids), _p(dist), C.byref(total))
+        if count_only:
+            self._ck(call(0, None, None))
+            return offsets, np.empty(0, np.uint32), np.empty(0, np.float64)
+        n = max(1 << 16, 64 * nq) if cap is None else int(cap)
+        for attempt in range(2):
+            ids, dist = np.empty(max(n, 1), np.uint32), np.empty(max(n, 1), np.float64)
+            rc = call(n, ids, dist)
             if rc == E_NOMEM and cap is None and attempt == 0 and total.value > n:
                 n = total.value                              # sized to the total exactly: the second and last call
                 continue

@@ -23,7 +23,8 @@ SOURCES = {
     "hx_mfma.hip": ["hx_ops.h"],
     "hx_sparse.hip": ["hx_ops.h"],
     "hx_exact.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h", "hx_exact_plan.h"],
-    "hx_range.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h"],
+    "hx_range.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h", "hx_range_core.h"],
+    "hx_range_g.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h", "hx_range_core.h", "hx_range_plan.h"],
     "hx_rerank.hip": ["hx_ops.h", "hx_exact_core.h"],
     "hx_sidecar.hip": ["hx_ops.h", "hx_fused_core.h"],
     "hx_group.hip": [],

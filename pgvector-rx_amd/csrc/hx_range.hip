@@ -19,10 +19,7 @@
 // <-> with `<` / `<=` on an f32 engine that keeps the 8-bit sidecar (k_range_scan_sc, query tiles of 1 and 4; hx_exact_sc.h): a wave
 //   first reads the code rows of SC_ROWS rows and evaluates only those whose proven lower bound does not already lie past the radius, in row
 //   order, through the same ex_eval and ballot + prefix count.  Count-only calls and the window pass take the same kernel.
-#include "hx_exact_sc.h"
-
-#include <hipcub/hipcub.hpp>
-#include <vector>
+#include "hx_range_core.h"
 
 namespace {
 
@@ -36,11 +33,6 @@ struct RgArgs {
     const uint64_t *seg_base; uint64_t w0, w1;                // window pass (seg_base != nullptr): CSR position of a segment's first hit, window
     uint64_t *okey; uint32_t *oid;                            // staging (pass 1) or window output; oid == nullptr: count only, okey may be
 };
-
-__device__ __forceinline__ uint32_t rg_below(uint64_t m)    // set bits of m below this lane
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // Q queries x one row slice of EX_WAVES segments.  RPS = 64 / LPR rows per wave slot, RIF slots per wave round.
 template <class OP, int HOP, int LPR, int RIF, int Q>
@@ -211,32 +203,6 @@ k_range_scan_sc(const RgArgs a, const ScArgs c)
     }
     __syncthreads();
     if (threadIdx.x == 0) { atomicAdd(c.stats, (unsigned long long)st_coded); atomicAdd(c.stats + 1, (unsigned long long)st_fetched); }
-}
-
-// the staged segments that did not overflow, each to its CSR position when that lies in [w0, w1); one wave per segment
-__global__ void __launch_bounds__(256)
-k_range_gather(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sid, const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ seg_base,
-               uint64_t nseg, uint32_t scap, uint64_t w0, uint64_t w1, uint64_t *__restrict__ okey, uint32_t *__restrict__ oid)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t seg = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); seg < nseg; seg += (uint64_t)gridDim.x * 4) {
-        const uint32_t c = cnt[seg];
-        const uint64_t sb = seg_base[seg];
-        if (c == 0 || c > scap || sb >= w1 || sb + c <= w0) continue;
-        const uint32_t lo = sb < w0 ? (uint32_t)(w0 - sb) : 0u, hi = (uint32_t)std::min<uint64_t>(c, w1 - sb);
-        for (uint32_t t = lo + lane; t < hi; t += 64) {
-            const uint64_t d = sb + t - w0;
-            oid[d] = sid[seg * scap + t];
-            if (okey) okey[d] = skey[seg * scap + t];
-        }
-    }
-}
-
-// order keys -> the values hx_exact_search returns (in place: the key array becomes the f64 array)
-__global__ void k_range_values(uint64_t *__restrict__ key, uint64_t n, int neg_zero)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) key[i] = __builtin_bit_cast(uint64_t, ex_val(key[i], neg_zero != 0));
 }
 
 // filter bitmap -> row-id list in row order: word w's passing rows go to out[woff[w] ..] (woff: exclusive scan of the words' popcounts)
