@@ -203,7 +203,9 @@ int hx_last_kernel_ms(hx_engine *e, float *ms);
  * 8 = range scans (hx_exact_range, hx_exact_range_filtered): units = distances evaluated (passing rows x nq; with a filter per query the sum
  *     over the queries of their filter's passing rows), ms = the summed kernel time of the calls,
  * 9 = exact re-rank (hx_exact_rerank): units = distances evaluated (candidates listed), ms = the summed kernel time of the calls,
- * 10 = vector -> halfvec casts (hx_append_rows_halfvec, hx_set_queries_halfvec): units = elements cast. */
+ * 10 = vector -> halfvec casts (hx_append_rows_halfvec, hx_set_queries_halfvec): units = elements cast,
+ * 11 = filter-set builds and appends (hx_filterset_create_*, hx_filterset_append_labels): units = rows partitioned (from bitmaps: rows listed),
+ *      ms = the summed kernel time (not the uploads); the scans never move it. */
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset);
 
 /* ---- exact k-NN scan: the sequential-scan plan of `SELECT ... ORDER BY v <op> q LIMIT k` ---------------------------------------------
@@ -343,6 +345,64 @@ int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const double *radius,
                             uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
                             int order, uint64_t cap,
                             uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
+
+/* ---- filter sets: the filters of the exact scans, resident on the device ------------------------------------------------------------------
+ * A set covers rows [first_row, first_row + n_rows) and holds, per filter f in [0, n_filters), the ascending list of the row ids it passes:
+ * 4 B per listed row in one uint32 array plus CSR uint64 offsets, of which the host keeps a copy (planning a scan needs no device round trip).
+ * It is made once -- a tenant column changes far less often than queries arrive -- extended as rows are appended, and named by the two _set scans
+ * below in place of host bitmaps.  It borrows the engine, which must outlive it (as hx_index does).
+ *   hx_filterset_create_labels        : row first_row + i is in filter labels[i]; HX_NO_LABEL: in no filter (a NULL tenant).  Filters are disjoint.
+ *   hx_filterset_create_labels_device : the same with the label column in device memory (the device is synchronised first, as for
+ *                                       hx_append_rows_device).
+ *   hx_filterset_create_bitmaps       : filters[f] is a bitmap in hx_exact_search_filtered's layout (ceil(n_rows / 64) words, stray bits past n_rows
+ *                                       ignored); NULL = an empty filter; filters may overlap.  Compacted in chunks of at most 64 bitmaps, so the
+ *                                       staging memory does not grow with n_filters.
+ *   hx_filterset_append_labels        : extends the coverage by the next n rows, which must already be in the engine (HX_E_ARG otherwise).  The set
+ *                                       then is what a set created over the whole range would be; any set accepts it, bitmap-made ones included.
+ *   hx_filterset_info                 : any output may be NULL; n_listed = the sum of the list lengths.  Works on an invalid set.
+ *   hx_filterset_counts               : the list lengths of filters [first, first + n), from the host's offsets.
+ *   hx_filterset_read                 : *n_out = the length of filter's list; the list is copied to ids_out when it fits cap, HX_E_NOMEM
+ *                                       ("capacity exceeded", *n_out still filled) when not.  ids_out may be NULL with cap == 0.
+ *   hx_filterset_destroy              : works on an invalid set.
+ * Invalidation: an hx_pop_rows that removes a covered row makes the set invalid for good: every later use returns HX_E_STATE, even after rows
+ *   are appended again (their labels are not the set's).  A pop that only removes rows past the coverage (the build's duplicate path: append, then
+ *   pop) leaves it valid.
+ * HX_E_ARG, checked before a device is touched and before anything is allocated: NULL engine, NULL out, NULL labels / filters with n_rows > 0;
+ *   n_filters == 0 or > HX_FILTERSET_MAX_FILTERS; a row range past the stored rows or past 2^32 - 1 (hx_exact_search's messages).
+ * A label >= n_filters that is not HX_NO_LABEL is HX_E_ARG too; it is found on the device (the partition kernels bound-check every label, write
+ *   nothing for a bad one and report the first), hx_last_error names that row, no set is created and an appended-to set is left unchanged.
+ * Partition: up to 1024 filters, per-wave tile histograms in LDS, one scan over (label, tile) and a scatter whose in-tile rank comes from wave
+ *   ballots: two reads of the label column, no sort, no global atomic on an output position; above, a stable radix sort of (label, row id) over
+ *   ceil(log2(n_filters + 1)) key bits and one boundary search.  hx_kernel_stats kind 11 counts the builds and appends. */
+typedef struct hx_filterset hx_filterset;
+#define HX_FILTERSET_MAX_FILTERS (1u << 20)
+#define HX_NO_LABEL 0xFFFFFFFFu
+int hx_filterset_create_labels(hx_engine *e, uint64_t first_row, uint64_t n_rows, uint32_t n_filters,
+                               const uint32_t *labels_host, hx_filterset **out);
+int hx_filterset_create_labels_device(hx_engine *e, uint64_t first_row, uint64_t n_rows, uint32_t n_filters,
+                                      const uint32_t *labels_dev, hx_filterset **out);
+int hx_filterset_create_bitmaps(hx_engine *e, uint64_t first_row, uint64_t n_rows, uint32_t n_filters,
+                                const uint64_t *const *filters, hx_filterset **out);
+int hx_filterset_append_labels(hx_filterset *s, uint64_t n, const uint32_t *labels_host);
+int hx_filterset_info(const hx_filterset *s, uint64_t *first_row, uint64_t *n_rows, uint32_t *n_filters, uint64_t *n_listed);
+int hx_filterset_counts(const hx_filterset *s, uint32_t first, uint32_t n, uint64_t *counts_out);
+int hx_filterset_read(hx_filterset *s, uint32_t filter, uint64_t cap, uint32_t *ids_out, uint64_t *n_out);
+int hx_filterset_destroy(hx_filterset *s);
+
+/* ---- the per-query-filter scans on a filter set -----------------------------------------------------------------------------------------------
+ * Definition: the outputs equal, byte for byte, those of hx_exact_search_filtered / hx_exact_range_filtered called with the set's row range and
+ * the bitmaps the set represents.  filter_of[i] is in [-1, n_filters of the set): -1 = every row of the set's range; NULL = -1 for all.  A call
+ * may reference at most HX_EXACT_MAX_FILTERS DISTINCT filters, however many the set holds (HX_E_ARG above; the host splits the batch).  A set of
+ * another engine: HX_E_ARG; an invalid set: HX_E_STATE; everything else is rejected as the twin rejects it, with its message.
+ * No bitmap is uploaded, no popcount runs (the counts are the offsets) and nothing is compacted: the scan kernels read the set's lists in place.
+ * One distinct filter: the path of hx_exact_search / hx_exact_range with the resident list standing where the compacted bitmap stands -- the same
+ * sidecar decision, the same accounting.  hx_kernel_stats kinds 7 and 8 count as for the twins less the compaction launch; hx_exact_sidecar_stats
+ * moves as for the twin. */
+int hx_exact_search_set(hx_engine *e, int op, uint32_t first_query, uint32_t nq, const hx_filterset *s, const int32_t *filter_of,
+                        uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out);
+int hx_exact_range_set(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
+                       const hx_filterset *s, const int32_t *filter_of, int order, uint64_t cap,
+                       uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out);
 
 /* ---- exact re-rank of per-query candidate lists: the outer `ORDER BY v <op> q LIMIT k` over a subquery's rows ----------------------------
  * Per query slot first_query + i, the first k rows of

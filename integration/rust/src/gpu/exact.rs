@@ -96,3 +96,71 @@ pub fn exact_range_filtered_gpu(e: *mut hx_engine, op: c_int, cmp: c_int, radius
         })
         .collect()
 }
+
+/// The tenant column of a table as a filter set: made when the host first sees the table (`labels[i]`: the tenant number of row `i`,
+/// `HX_NO_LABEL` for a NULL tenant), extended by `filterset_append_gpu` on insert, dropped and rebuilt after a vacuum that renumbers rows.
+pub fn filterset_from_labels_gpu(e: *mut hx_engine, labels: &[u32], n_filters: u32) -> *mut hx_filterset {
+    let mut s: *mut hx_filterset = std::ptr::null_mut();
+    unsafe { ck(e, hx_filterset_create_labels(e, 0, labels.len() as u64, n_filters, labels.as_ptr(), &mut s)) };
+    s
+}
+
+/// The labels of the rows appended to the engine since the set was made or last extended.
+pub fn filterset_append_gpu(e: *mut hx_engine, s: *mut hx_filterset, labels: &[u32]) {
+    unsafe { ck(e, hx_filterset_append_labels(s, labels.len() as u64, labels.as_ptr())) };
+}
+
+fn filter_of_set(filter_of: &[Option<u32>]) -> Vec<i32> {
+    filter_of.iter().map(|f| f.map_or(-1, |f| f as i32)).collect()
+}
+
+/// `exact_search_filtered_gpu` over the rows the set covers, the set's resident lists standing for the bitmaps: `filter_of[i]` is query `i`'s
+/// tenant number, `None` for no `WHERE`.  The executor splits batches that name more than `HX_EXACT_MAX_FILTERS` distinct tenants.
+pub fn exact_search_set_gpu(e: *mut hx_engine, op: c_int, k: u32, s: *const hx_filterset, filter_of: &[Option<u32>]) -> Vec<ExactRows> {
+    let nq = filter_of.len();
+    let of = filter_of_set(filter_of);
+    let mut ids = vec![0u32; nq * k as usize];
+    let mut dist = vec![0f64; nq * k as usize];
+    let mut counts = vec![0u32; nq];
+    unsafe {
+        ck(e, hx_exact_search_set(e, op, 0, nq as u32, s, of.as_ptr(), k, ids.as_mut_ptr(), dist.as_mut_ptr(), counts.as_mut_ptr()));
+    }
+    (0..nq)
+        .map(|q| {
+            let (a, b) = (q * k as usize, q * k as usize + counts[q] as usize);
+            ExactRows { ids: ids[a..b].to_vec(), distances: dist[a..b].to_vec() }
+        })
+        .collect()
+}
+
+/// `exact_range_filtered_gpu` over the rows the set covers, the set's resident lists standing for the bitmaps.
+pub fn exact_range_set_gpu(e: *mut hx_engine, op: c_int, cmp: c_int, radius: &[f64], s: *const hx_filterset, filter_of: &[Option<u32>],
+                           order: c_int) -> Vec<ExactRows> {
+    let nq = filter_of.len();
+    assert!(radius.len() == nq, "one radius per query");
+    let of = filter_of_set(filter_of);
+    let mut offsets = vec![0u64; nq + 1];
+    let mut total = 0u64;
+    unsafe {
+        ck(
+            e,
+            hx_exact_range_set(e, op, cmp, radius.as_ptr(), 0, nq as u32, s, of.as_ptr(), order, 0, offsets.as_mut_ptr(), std::ptr::null_mut(),
+                               std::ptr::null_mut(), &mut total),
+        );
+    }
+    let mut ids = vec![0u32; total as usize];
+    let mut dist = vec![0f64; total as usize];
+    unsafe {
+        ck(
+            e,
+            hx_exact_range_set(e, op, cmp, radius.as_ptr(), 0, nq as u32, s, of.as_ptr(), order, total, offsets.as_mut_ptr(), ids.as_mut_ptr(),
+                               dist.as_mut_ptr(), &mut total),
+        );
+    }
+    (0..nq)
+        .map(|q| {
+            let (a, b) = (offsets[q] as usize, offsets[q + 1] as usize);
+            ExactRows { ids: ids[a..b].to_vec(), distances: dist[a..b].to_vec() }
+        })
+        .collect()
+}

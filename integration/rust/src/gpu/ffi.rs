@@ -17,6 +17,10 @@ pub struct hx_engine {
 pub struct hx_index {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct hx_filterset {
+    _private: [u8; 0],
+}
 
 pub const HX_ABI_VERSION: c_int = 1;
 // enum hx_dtype
@@ -51,7 +55,9 @@ pub const HX_OP_L1: c_int = 3; // <+>
 pub const HX_OP_HAMMING: c_int = 4; // <~>
 pub const HX_OP_JACCARD: c_int = 5; // <%>
 pub const HX_EXACT_MAX_K: u32 = 1024;
-pub const HX_EXACT_MAX_FILTERS: u32 = 64; // filters per hx_exact_search_filtered call
+pub const HX_EXACT_MAX_FILTERS: u32 = 64; // filters per hx_exact_search_filtered call; distinct filters per hx_exact_search_set call
+pub const HX_FILTERSET_MAX_FILTERS: u32 = 1 << 20; // filters of one filter set
+pub const HX_NO_LABEL: u32 = 0xFFFF_FFFF; // a row in no filter of a filter set (a NULL tenant)
 // hx_cmp: the comparison of a range scan, v <op> q <cmp> radius (hx_exact_range)
 pub const HX_CMP_LT: c_int = 0; // <
 pub const HX_CMP_LE: c_int = 1; // <=
@@ -124,6 +130,24 @@ extern "C" {
     pub fn hx_exact_range_filtered(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, first_row: u64,
                                    n_rows: u64, n_filters: u32, filters: *const *const u64, filter_of: *const i32, order: c_int, cap: u64,
                                    offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64, total_out: *mut u64) -> c_int;
+    // filter sets: the filters of the exact scans as row-id lists resident on the device, from a label column or bitmaps; appended to on insert
+    pub fn hx_filterset_create_labels(e: *mut hx_engine, first_row: u64, n_rows: u64, n_filters: u32, labels_host: *const u32,
+                                      out: *mut *mut hx_filterset) -> c_int;
+    pub fn hx_filterset_create_labels_device(e: *mut hx_engine, first_row: u64, n_rows: u64, n_filters: u32, labels_dev: *const u32,
+                                             out: *mut *mut hx_filterset) -> c_int;
+    pub fn hx_filterset_create_bitmaps(e: *mut hx_engine, first_row: u64, n_rows: u64, n_filters: u32, filters: *const *const u64,
+                                       out: *mut *mut hx_filterset) -> c_int;
+    pub fn hx_filterset_append_labels(s: *mut hx_filterset, n: u64, labels_host: *const u32) -> c_int;
+    pub fn hx_filterset_info(s: *const hx_filterset, first_row: *mut u64, n_rows: *mut u64, n_filters: *mut u32, n_listed: *mut u64) -> c_int;
+    pub fn hx_filterset_counts(s: *const hx_filterset, first: u32, n: u32, counts_out: *mut u64) -> c_int;
+    pub fn hx_filterset_read(s: *mut hx_filterset, filter: u32, cap: u64, ids_out: *mut u32, n_out: *mut u64) -> c_int;
+    pub fn hx_filterset_destroy(s: *mut hx_filterset) -> c_int;
+    // the per-query-filter scans with a filter set in place of host bitmaps: the same bytes, nothing uploaded or compacted
+    pub fn hx_exact_search_set(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, s: *const hx_filterset, filter_of: *const i32, k: u32,
+                               ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;
+    pub fn hx_exact_range_set(e: *mut hx_engine, op: c_int, cmp: c_int, radius: *const f64, first_query: u32, nq: u32, s: *const hx_filterset,
+                              filter_of: *const i32, order: c_int, cap: u64, offsets_out: *mut u64, ids_out: *mut u32, dist_out: *mut f64,
+                              total_out: *mut u64) -> c_int;
     // exact re-rank of per-query candidate lists (the outer ORDER BY v <op> q LIMIT k over an index scan's candidates)
     pub fn hx_exact_rerank(e: *mut hx_engine, op: c_int, first_query: u32, nq: u32, cand_offsets: *const u64, cand_ids: *const u32, k: u32,
                            ids_out: *mut u32, dist_out: *mut f64, counts_out: *mut u32) -> c_int;

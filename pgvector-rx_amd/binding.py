@@ -11,10 +11,14 @@ L2SQ, NEG_IP, L1, HAMMING, JACCARD = 0, 1, 2, 3, 4
 OP_L2, OP_NEG_IP, OP_COSINE, OP_L1, OP_HAMMING, OP_JACCARD = 0, 1, 2, 3, 4, 5   # hx_op: the SQL operators <-> <#> <=> <+> <~> <%>
 EXACT_MAX_K = 1024
 EXACT_MAX_FILTERS = 64                                 # hx_exact_search_filtered
+FILTERSET_MAX_FILTERS = 1 << 20                        # hx_filterset_create_*
+NO_LABEL = 0xFFFFFFFF                                  # HX_NO_LABEL: a row in no filter of a filter set
 CMP_LT, CMP_LE, CMP_GT, CMP_GE = 0, 1, 2, 3           # hx_cmp: v <op> q  <  <=  >  >=  radius
 SCAN_MAX_FILTERS, SCAN_STOP_PAST_RADIUS = 64, 1       # hx_index_search_filtered
 RANGE_BY_ROW, RANGE_BY_DISTANCE = 0, 1                 # hx_range_order: heap order, or the ORDER BY without LIMIT
+E_ARG = -1
 E_NOMEM = -3
+E_STATE = -6
 E_RANGE = -7                                           # a value out of range for the target type (the halfvec casts)
 CREATE_SCAN_ONLY = 1                                   # hx_create_ex: no index; vector / halfvec up to 16000 dims
 CREATE_NO_SIDECAR = 4                                  # hx_create_ex: no 8-bit row sidecar (f32 L2 engines keep one by default)
@@ -103,6 +107,16 @@ def lib():
         "hx_exact_range": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, vp, i32, u64, vp, vp, vp, vp]),
         "hx_exact_range_filtered": (i32, [vp, i32, i32, vp, u32, u32, u64, u64, u32, vp, vp, i32, u64, vp, vp, vp, vp]),
         "hx_exact_rerank": (i32, [vp, i32, u32, u32, vp, vp, u32, vp, vp, vp]),
+        "hx_filterset_create_labels": (i32, [vp, u64, u64, u32, vp, C.POINTER(vp)]),
+        "hx_filterset_create_labels_device": (i32, [vp, u64, u64, u32, vp, C.POINTER(vp)]),
+        "hx_filterset_create_bitmaps": (i32, [vp, u64, u64, u32, vp, C.POINTER(vp)]),
+        "hx_filterset_append_labels": (i32, [vp, u64, vp]),
+        "hx_filterset_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), C.POINTER(u64)]),
+        "hx_filterset_counts": (i32, [vp, u32, u32, vp]),
+        "hx_filterset_read": (i32, [vp, u32, u64, vp, C.POINTER(u64)]),
+        "hx_filterset_destroy": (i32, [vp]),
+        "hx_exact_search_set": (i32, [vp, i32, u32, u32, vp, vp, u32, vp, vp, vp]),
+        "hx_exact_range_set": (i32, [vp, i32, i32, vp, u32, u32, vp, vp, i32, u64, vp, vp, vp, vp]),
         "hx_index_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
         "hx_index_destroy": (i32, [vp]),
         "hx_index_last_error": (C.c_char_p, [vp]),
@@ -486,10 +500,124 @@ class Engine:
         t = int(total.value)
         return offsets, ids[:t], dist[:t]
 
+    def exact_search_set(self, op, k, fset, filter_of, first_query=0, nq=None):
+        """hx_exact_search_set: exact_search_filtered over the rows a FilterSet covers, with the set's resident lists in place of host bitmaps.
+        filter_of: per query the index of its filter in the set, -1 for none (None: -1 for all); at most EXACT_MAX_FILTERS distinct ones per
+        call.  Returns (ids, dist, counts): the bytes exact_search_filtered returns for the bitmaps the set represents."""
+        nq = self._nq - first_query if nq is None else nq
+        fo = None if filter_of is None else np.ascontiguousarray(filter_of, dtype=np.int32)
+        if fo is not None and (fo.ndim != 1 or len(fo) != nq):
+            raise ValueError("filter_of needs one entry per query")
+        ids = np.empty((nq, k), np.uint32)
+        dist = np.empty((nq, k), np.float64)
+        cnt = np.empty(nq, np.uint32)
+        self._ck(lib().hx_exact_search_set(self.h, op, first_query, nq, fset.h, _p(fo), k, _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
+
+    def exact_range_set(self, op, radius, fset, filter_of, cmp=CMP_LT, first_query=0, nq=None, ordered=False, count_only=False, cap=None,
+                        values=True):
+        """hx_exact_range_set: exact_range_filtered over the rows a FilterSet covers, with the set's resident lists in place of host bitmaps.
+        filter_of as in exact_search_set; radius: a scalar or one value per query; values=False: ids without values (dist comes back empty).
+        Returns (offsets, ids, dist) in CSR form: the bytes exact_range_filtered returns for the bitmaps the set represents.  cap=None: as in
+        exact_range."""
+        nq = self._nq - first_query if nq is None else nq
+        fo = None if filter_of is None else np.ascontiguousarray(filter_of, dtype=np.int32)
+        if fo is not None and (fo.ndim != 1 or len(fo) != nq):
+            raise ValueError("filter_of needs one entry per query")
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (nq,)))
+        offsets = np.zeros(nq + 1, np.uint64)
+        total = C.c_uint64()
+        order = RANGE_BY_DISTANCE if ordered else RANGE_BY_ROW
+        L = lib()
+
+        def call(n, ids, dist):
+            return L.hx_exact_range_set(self.h, op, cmp, _p(r), first_query, nq, fset.h, _p(fo), order, n, _p(offsets), _p(ids), _p(dist),
+                                        C.byref(total))
+        if count_only:
+            self._ck(call(0, None, None))
+            return offsets, np.empty(0, np.uint32), np.empty(0, np.float64)
+        n = max(1 << 16, 64 * nq) if cap is None else int(cap)
+        for attempt in range(2):
+            ids, dist = np.empty(max(n, 1), np.uint32), (np.empty(max(n, 1), np.float64) if values else None)
+            rc = call(n, ids, dist)
+            if rc == E_NOMEM and cap is None and attempt == 0 and total.value > n:
+                n = total.value                              # sized to the total exactly: the second and last call
+                continue
+            self._ck(rc)
+            break
+        t = int(total.value)
+        return offsets, ids[:t], (dist[:t] if values else np.empty(0, np.float64))
+
     def kernel_stats(self, kind, reset=False):
         l, u, ms = C.c_uint64(), C.c_uint64(), C.c_double()
         self._ck(lib().hx_kernel_stats(self.h, kind, C.byref(l), C.byref(u), C.byref(ms), int(reset)))
         return {"launches": l.value, "units": u.value, "ms": ms.value}
+
+
+class FilterSet:
+    """hx_filterset: the filters of the exact scans as row-id lists resident on the device (one ascending list per filter), made once from a label
+    column or from bitmaps and extended as rows are appended.  Engine.exact_search_set / exact_range_set take it in place of host bitmaps.  It
+    borrows the engine (and keeps it alive)."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.h = engine, handle
+
+    @classmethod
+    def from_labels(cls, engine, labels, n_filters, first_row=0, device_ptr=None, n_rows=None):
+        """Row first_row + i is in filter labels[i]; NO_LABEL: in no filter.  device_ptr: the uint32 label column in device memory instead
+        (n_rows entries; labels is ignored)."""
+        h = C.c_void_p()
+        if device_ptr is not None:
+            rc = lib().hx_filterset_create_labels_device(engine.h, first_row, int(n_rows), n_filters, C.c_void_p(device_ptr), C.byref(h))
+        else:
+            lb = _u32(labels)
+            rc = lib().hx_filterset_create_labels(engine.h, first_row, len(lb), n_filters, _p(lb), C.byref(h))
+        engine._ck(rc)
+        return cls(engine, h)
+
+    @classmethod
+    def from_bitmaps(cls, engine, filters, n_rows=None, first_row=0, packed=False):
+        """filters: a list of row masks as Engine.exact_search_filtered takes them (packed=True: uint64 word arrays); None: an empty filter."""
+        n_rows = engine.num_rows - first_row if n_rows is None else n_rows
+        words = [_row_words(f, n_rows, packed) for f in filters]
+        ptrs = (C.c_void_p * max(1, len(words)))(*[None if w is None else w.ctypes.data for w in words])
+        h = C.c_void_p()
+        engine._ck(lib().hx_filterset_create_bitmaps(engine.h, first_row, n_rows, len(words), ptrs, C.byref(h)))
+        return cls(engine, h)
+
+    def _ck(self, rc):
+        self.engine._ck(rc)
+
+    def append_labels(self, labels):
+        """Extends the coverage by the next len(labels) rows, which must already be in the engine."""
+        lb = _u32(labels)
+        self._ck(lib().hx_filterset_append_labels(self.h, len(lb), _p(lb)))
+
+    def info(self):
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        self._ck(lib().hx_filterset_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"first_row": a.value, "n_rows": b.value, "n_filters": c.value, "n_listed": d.value}
+
+    def counts(self, first=0, n=None):
+        n = self.info()["n_filters"] - first if n is None else n
+        out = np.empty(n, np.uint64)
+        self._ck(lib().hx_filterset_counts(self.h, first, n, _p(out)))
+        return out
+
+    def read(self, f):
+        """The ascending row ids filter f passes."""
+        n = int(self.counts(f, 1)[0])
+        out = np.empty(n, np.uint32)
+        got = C.c_uint64()
+        self._ck(lib().hx_filterset_read(self.h, f, n, _p(out) if n else None, C.byref(got)))
+        return out[:got.value]
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hx_filterset_destroy(self.h)
+            self.h = None
+
+    __del__ = close
 
 
 class Index:

@@ -26,6 +26,7 @@ SOURCES = {
     "hx_range.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h", "hx_range_core.h"],
     "hx_range_g.hip": ["hx_ops.h", "hx_exact_core.h", "hx_exact_sc.h", "hx_range_core.h", "hx_range_plan.h"],
     "hx_rerank.hip": ["hx_ops.h", "hx_exact_core.h"],
+    "hx_filterset.hip": [],
     "hx_sidecar.hip": ["hx_ops.h", "hx_fused_core.h"],
     "hx_group.hip": [],
     "hx_batch.hip": ["hx_ops.h"],

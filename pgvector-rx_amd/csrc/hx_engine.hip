@@ -494,6 +494,7 @@ int hx_destroy(hx_engine *e)
     if (!e) return HX_OK;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    hx_filterset_engine_gone(e);
     HxChannel &c = e->ch;
     HxMirror &mr = e->mirror;
     void *hp[] = {c.h_req, c.h_res, mr.h_stage, mr.io.h_io, mr.h_lk, e->grp.h_ctr, e->grp.h, e->bw.h, e->bw.h_ctr};
@@ -559,6 +560,8 @@ int hx_pop_rows(hx_engine *e, uint64_t n)
     if (!e) return HX_E_ARG;
     if (n > e->n_rows) return e->fail(HX_E_ARG, "cannot pop more rows than stored");
     e->n_rows -= n;
+    for (hx_filterset *s : e->sets)                              // a filter set that lost a covered row is invalid for good (hx_filterset.hip)
+        if (s->first_row + s->n_rows > e->n_rows) s->valid = false;
     return HX_OK;
 }
 
@@ -948,7 +951,7 @@ int hx_last_kernel_ms(hx_engine *e, float *ms) { if (!e || !ms) return HX_E_ARG;
 int hx_kernel_stats(hx_engine *e, int kind, uint64_t *launches, uint64_t *units, double *ms, int reset)
 {
     if (!e) return HX_E_ARG;
-    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : kind == 8 ? e->stat_range : kind == 9 ? e->stat_rerank : kind == 10 ? e->stat_cast : e->stat_mfma;
+    HxKernelStat &s = kind == 0 ? e->stat_dist : kind == 1 ? e->stat_pair : kind == 2 ? e->stat_fused : kind == 3 ? e->stat_links : kind == 5 ? e->stat_scan : kind == 6 ? e->stat_wsel : kind == 7 ? e->stat_exact : kind == 8 ? e->stat_range : kind == 9 ? e->stat_rerank : kind == 10 ? e->stat_cast : kind == 11 ? e->stat_fset : e->stat_mfma;
     if (kind == 5 && reset) { e->scan_epoch_set = false; e->scan_last_end = 0.0; }
     if (launches) *launches = s.launches;
     if (units) *units = s.units;

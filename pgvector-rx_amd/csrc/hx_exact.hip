@@ -502,15 +502,11 @@ hipError_t exg_scan(hx_engine *e, int op, const ExGArgs &a, uint32_t Q, uint32_t
     }
 }
 
-} // namespace
-
-// =================================================================================================
-// C ABI
-// =================================================================================================
-extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
-                               const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+// hx_exact_search with its filter source chosen: a host bitmap (row_pass: popcounted, uploaded and compacted here), an id list already on the
+// device (list: a filter set's; it stands where the compacted bitmap stands, and nothing is uploaded or compacted), or neither
+int ex_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows, const uint64_t *row_pass, const HxIdList *list,
+              uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
 {
-    if (!e) return HX_E_ARG;
     const bool bit = e->dtype == HX_BIT;
     if (op < HX_OP_L2 || op > HX_OP_JACCARD || bit != (op == HX_OP_HAMMING || op == HX_OP_JACCARD))
         return e->fail(HX_E_ARG, "operator is not defined for this column type");
@@ -522,7 +518,7 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
     if (nq == 0) return HX_OK;
 
     const uint64_t n_words = (n_rows + 63) / 64;
-    uint64_t n_pass = n_rows;
+    uint64_t n_pass = list ? list->n : n_rows;
     if (row_pass) {
         n_pass = 0;
         for (uint64_t w = 0; w < n_words; w++) {
@@ -576,7 +572,7 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
         e->cap_exact = need;
     }
     uint8_t *d = e->d_exact;
-    uint32_t *d_ids = row_pass ? (uint32_t *)d : nullptr;
+    const uint32_t *d_ids = row_pass ? (const uint32_t *)d : list ? list->d : nullptr;
     uint64_t launches = 0; double ms = 0.0;
     if (row_pass) {
         HX_HIP(e, hipMemsetAsync(d + o_ctr, 0, 4, e->stream));
@@ -585,7 +581,7 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
     if (e->timing) HX_HIP(e, hipEventRecord(e->ev0, e->stream));   // kind 7 = kernel time: the bitmap upload is not in it
     if (row_pass) {
         hipLaunchKernelGGL(k_exact_compact, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, e->stream,
-                           (const uint64_t *)(d + o_words), n_words, n_rows, (uint32_t)first_row, d_ids, (uint32_t *)(d + o_ctr));
+                           (const uint64_t *)(d + o_words), n_words, n_rows, (uint32_t)first_row, (uint32_t *)d, (uint32_t *)(d + o_ctr));
         HX_HIP(e, hipGetLastError());
         launches++;
     }
@@ -644,11 +640,12 @@ extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint3
     return HX_OK;
 }
 
-extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
-                                        uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
-                                        uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+// The body of hx_exact_search_filtered and hx_exact_search_set.  The filter source is host bitmaps (filters; set == nullptr) or the resident lists of
+// a filter set (set; filters unused): then the counts are the set's offsets, nothing is uploaded or compacted and the set's id array is the id base.
+int exf_run(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows, uint32_t n_filters,
+            const uint64_t *const *filters, const hx_filterset *set, const int32_t *filter_of, uint32_t k, uint32_t *ids_out, double *dist_out,
+            uint32_t *counts_out)
 {
-    if (!e) return HX_E_ARG;
     const bool bit = e->dtype == HX_BIT;
     if (op < HX_OP_L2 || op > HX_OP_JACCARD || bit != (op == HX_OP_HAMMING || op == HX_OP_JACCARD))
         return e->fail(HX_E_ARG, "operator is not defined for this column type");
@@ -657,8 +654,17 @@ extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_que
     if (first_row + n_rows > 0xFFFFFFFFull) return e->fail(HX_E_ARG, "row range past 2^32 - 1");
     if ((uint64_t)first_query + nq > e->n_queries) return e->fail(HX_E_ARG, "query range past the uploaded query slots");
     if (!ids_out || !dist_out || !counts_out) return e->fail(HX_E_ARG, "NULL output");
-    if (n_filters > HX_EXACT_MAX_FILTERS) return e->fail(HX_E_ARG, "more than HX_EXACT_MAX_FILTERS filters");
-    if (n_filters > 0 && !filters) return e->fail(HX_E_ARG, "NULL filters with n_filters > 0");
+    std::vector<int32_t> local_of; uint32_t set_f[HX_EXACT_MAX_FILTERS];   // a set: the call's distinct filters stand for the bitmaps
+    if (set) {
+        const int rc = hx_filterset_localize(e, set, nq, filter_of, local_of, set_f, &n_filters);
+        if (rc) return rc;
+        if (filter_of) filter_of = local_of.data();
+    } else {
+        if (n_filters > HX_EXACT_MAX_FILTERS) return e->fail(HX_E_ARG, "more than HX_EXACT_MAX_FILTERS filters");
+        if (n_filters > 0 && !filters) return e->fail(HX_E_ARG, "NULL filters with n_filters > 0");
+    }
+    auto set_off = [&](uint32_t v) { return set->off[set_f[v - 1]]; };
+    auto set_cnt = [&](uint32_t v) { return set->off[(size_t)set_f[v - 1] + 1] - set->off[set_f[v - 1]]; };
     // group v + 1 holds the queries of filter v (v = -1: no filter)
     uint32_t g_nq[HX_EXACT_MAX_FILTERS + 1] = {};
     if (!filter_of) g_nq[0] = nq;
@@ -666,12 +672,16 @@ extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_que
         for (uint32_t i = 0; i < nq; i++) {
             const int32_t f = filter_of[i];
             if (f < -1 || f >= (int32_t)n_filters) return e->fail(HX_E_ARG, "filter_of entry outside [-1, n_filters)");
-            if (f >= 0 && !filters[f]) return e->fail(HX_E_ARG, "a query references a NULL filter");
+            if (f >= 0 && !set && !filters[f]) return e->fail(HX_E_ARG, "a query references a NULL filter");
             g_nq[f + 1]++;
         }
     if (nq == 0) return HX_OK;
     for (uint32_t v = 0; v <= n_filters; v++)                  // one distinct filter: this is hx_exact_search with that bitmap
-        if (g_nq[v] == nq) return hx_exact_search(e, op, first_query, nq, first_row, n_rows, v ? filters[v - 1] : nullptr, k, ids_out, dist_out, counts_out);
+        if (g_nq[v] == nq) {
+            const HxIdList one{set && v ? set->d_ids + set_off(v) : nullptr, set && v ? set_cnt(v) : 0};
+            return ex_search(e, op, first_query, nq, first_row, n_rows, v && !set ? filters[v - 1] : nullptr, v && set ? &one : nullptr, k, ids_out, dist_out,
+                             counts_out);
+        }
 
     const uint64_t n_words = (n_rows + 63) / 64;
     uint64_t g_pass[HX_EXACT_MAX_FILTERS + 1] = {}, g_ids[HX_EXACT_MAX_FILTERS + 1], total_ids = 0, units = 0;
@@ -680,6 +690,7 @@ extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_que
     g_pass[0] = n_rows; g_ids[0] = EX_NO_IDS;
     for (uint32_t v = 1; v <= n_filters; v++) {
         if (!g_nq[v]) continue;
+        if (set) { g_pass[v] = set_cnt(v); g_ids[v] = set_off(v); continue; }
         const uint64_t *words = filters[v - 1];
         uint64_t n = 0;
         for (uint64_t w = 0; w < n_words; w++) {
@@ -748,7 +759,7 @@ extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_que
     }
     ExGArgs a{};
     a.rows = e->d_rows; a.queries = e->d_queries; a.pitch = pitch; a.cap_sp = (uint32_t)std::min(e->dim, HX_SPARSE_MAX_NNZ);
-    a.ids = (const uint32_t *)d; a.row0 = (uint32_t)first_row; a.k = k;
+    a.ids = set ? set->d_ids : (const uint32_t *)d; a.row0 = (uint32_t)first_row; a.k = k;
     a.gkey = (uint64_t *)(d + o_key); a.gid = (uint32_t *)(d + o_id); a.gcnt = (uint32_t *)(d + o_cnt);
     a.slots = (const uint32_t *)(d + o_slots);
     std::vector<uint32_t> h_ids((size_t)p.max_nq * k), h_cnt(p.max_nq);
@@ -784,6 +795,34 @@ extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_que
         e->stat_exact.launches += launches; e->stat_exact.units += units; e->stat_exact.ms += ms;
     }
     return HX_OK;
+}
+
+} // namespace
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" int hx_exact_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                               const uint64_t *row_pass, uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+{
+    if (!e) return HX_E_ARG;
+    return ex_search(e, op, first_query, nq, first_row, n_rows, row_pass, nullptr, k, ids_out, dist_out, counts_out);
+}
+
+extern "C" int hx_exact_search_filtered(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                                        uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
+                                        uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+{
+    if (!e) return HX_E_ARG;
+    return exf_run(e, op, first_query, nq, first_row, n_rows, n_filters, filters, nullptr, filter_of, k, ids_out, dist_out, counts_out);
+}
+
+extern "C" int hx_exact_search_set(hx_engine *e, int op, uint32_t first_query, uint32_t nq, const hx_filterset *s, const int32_t *filter_of,
+                                   uint32_t k, uint32_t *ids_out, double *dist_out, uint32_t *counts_out)
+{
+    if (!e) return HX_E_ARG;
+    if (const int rc = hx_filterset_usable(e, s)) return rc;
+    return exf_run(e, op, first_query, nq, s->first_row, s->n_rows, 0, nullptr, s, filter_of, k, ids_out, dist_out, counts_out);
 }
 
 extern "C" int hx_exact_sidecar_stats(hx_engine *e, uint64_t *rows_coded, uint64_t *rows_fetched, int reset)

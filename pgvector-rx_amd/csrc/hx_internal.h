@@ -155,6 +155,14 @@ uint32_t hx_rec_words(uint32_t m);                      // 32-bit words per memb
 struct HxWselWork { void *d_wl = nullptr; uint32_t *d_cnt = nullptr, *d_slot = nullptr, *d_task = nullptr; uint8_t *d_layer = nullptr; unsigned long long *d_counters = nullptr;
                     size_t cap_prob = 0; uint32_t cap_ef = 0; };
 struct hx_engine;
+// A filter set (hx_filterset.hip): one ascending row-id list per filter, CSR, resident on the device.  off is the host's copy of the offsets
+// (n_filters + 1 entries): the scans plan from it without a device round trip.  e == nullptr: the engine was destroyed first.
+struct hx_filterset {
+    hx_engine *e = nullptr; uint64_t first_row = 0, n_rows = 0; uint32_t n_filters = 0; bool valid = true;
+    uint32_t *d_ids = nullptr; uint64_t *d_off = nullptr; std::vector<uint64_t> off;
+};
+// a row-id list in device memory standing where a scan's compacted bitmap stands (n may be 0)
+struct HxIdList { const uint32_t *d; uint64_t n; };
 static inline uint32_t hx_xrec_words(uint32_t m) { return (3u + 4u * m + 3u) & ~3u; }   // list record of the multi-GPU exchange: target, layer, cnt, ids[2m], d[2m]
 int hx_group_stage(hx_engine *e, uint32_t n_ops, HxGroupWork &w, unsigned long long **keys, uint32_t **op_new, float **op_d);
 int hx_group_reserve(hx_engine *e, uint32_t n_ops, HxGroupWork &w);
@@ -176,6 +184,7 @@ struct hx_engine {
     HxKernelStat stat_range; uint8_t *d_range = nullptr; size_t cap_range = 0;   // range scans (hx_range.hip): kind 8 counters, device scratch
     HxKernelStat stat_rerank; uint8_t *d_rerank = nullptr; size_t cap_rerank = 0;   // exact re-rank (hx_rerank.hip): kind 9 counters, device scratch
     HxKernelStat stat_cast; bool scan_only = false;                               // kind 10: vector -> halfvec casts; HX_CREATE_SCAN_ONLY (no index, no pair kernels)
+    HxKernelStat stat_fset; std::vector<hx_filterset *> sets;                     // kind 11: filter-set builds and appends; the live sets (hx_filterset.hip), walked by hx_pop_rows
     // 8-bit row sidecar (hx_sidecar.hip): f32 L2 engines with 64-lane rows, unless HX_CREATE_NO_SIDECAR.  codes [capacity][sc_pitch],
     // {lo, step, e_x, 0} per row; sc_rows / sc_rej: f32 rows the traversal fetched / rows the bound rejected (hx_sidecar_stats)
     uint8_t *d_sc_codes = nullptr; float *d_sc_meta = nullptr; uint32_t sc_pitch = 0; uint64_t sc_rows = 0, sc_rej = 0;
@@ -258,6 +267,20 @@ struct hx_engine {
 
 // hx_sidecar.hip: (re-)encodes the sidecar of rows [first, first + n) on the engine stream (no-op without a sidecar)
 int hx_sidecar_encode(hx_engine *e, uint64_t first, uint64_t n);
+
+// hx_range.hip: hx_exact_range with its filter source chosen: a host bitmap (row_pass), a resident row-ordered id list (list), or neither
+int hx_exact_range_src(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                       const uint64_t *row_pass, const HxIdList *list, int order, uint64_t cap, uint64_t *offsets_out, uint32_t *ids_out,
+                       double *dist_out, uint64_t *total_out);
+// hx_range_g.hip: k_range_compact_g for n (<= HX_EXACT_MAX_FILTERS) bitmaps of n_words words and per-word offsets each -> the lists at out + base[i]
+hipError_t hx_range_compact_lists(hx_engine *e, const uint64_t *d_words, const uint32_t *d_woff, uint64_t n_words, uint64_t n_rows, uint32_t row0,
+                                  uint32_t *out, const uint64_t *base, uint32_t n);
+// hx_filterset.hip: what a _set scan checks of its set and filter_of (HX_E_ARG / HX_E_STATE with the message set), and the call's distinct filters:
+// set_f[0 .. *n_distinct) ascending, local_of[i] = the place of filter_of[i] in set_f (-1 stays -1; empty when filter_of is NULL)
+int hx_filterset_localize(hx_engine *e, const hx_filterset *s, uint32_t nq, const int32_t *filter_of, std::vector<int32_t> &local_of,
+                          uint32_t set_f[HX_EXACT_MAX_FILTERS], uint32_t *n_distinct);
+int hx_filterset_usable(hx_engine *e, const hx_filterset *s);
+void hx_filterset_engine_gone(hx_engine *e);                  // hx_destroy: frees the device arrays of the engine's live sets and orphans them
 
 // hx_sparse.hip: the sparsevec kernels (same request arrays as K1 / K2)
 #define HX_SPARSE_MAX_NNZ 1000

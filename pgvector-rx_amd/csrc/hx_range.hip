@@ -286,8 +286,11 @@ hipError_t rg_scan(hx_engine *e, int op, const RgArgs &a, uint32_t Q, uint32_t t
 // =================================================================================================
 // C ABI
 // =================================================================================================
-extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
-                              const uint64_t *row_pass, int order, uint64_t cap, uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
+// hx_exact_range with its filter source chosen: a host bitmap (row_pass: popcounted, uploaded and compacted here), a row-ordered id list already
+// on the device (list: a filter set's; it stands where the compacted bitmap stands, and nothing is uploaded or compacted), or neither
+int hx_exact_range_src(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                       const uint64_t *row_pass, const HxIdList *list, int order, uint64_t cap, uint64_t *offsets_out, uint32_t *ids_out,
+                       double *dist_out, uint64_t *total_out)
 {
     if (!e) return HX_E_ARG;
     const bool bit = e->dtype == HX_BIT;
@@ -308,7 +311,7 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
     if (nq == 0) return HX_OK;
     const uint64_t n_words = (n_rows + 63) / 64;
     std::vector<uint32_t> woff;
-    uint64_t n_pass = n_rows;
+    uint64_t n_pass = list ? list->n : n_rows;
     if (row_pass) {                                            // the filter's per-word offsets: popcounts, exclusive scan
         woff.resize(n_words);
         n_pass = 0;
@@ -397,7 +400,7 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
 
     RgArgs a{};
     a.rows = e->d_rows; a.queries = e->d_queries; a.pitch = pitch; a.cap_sp = (uint32_t)std::min(e->dim, HX_SPARSE_MAX_NNZ);
-    a.ids = row_pass ? (const uint32_t *)d : nullptr; a.row0 = (uint32_t)first_row; a.n = (uint32_t)n_pass; a.wper = wper; a.G = G;
+    a.ids = row_pass ? (const uint32_t *)d : list ? list->d : nullptr; a.row0 = (uint32_t)first_row; a.n = (uint32_t)n_pass; a.wper = wper; a.G = G;
     a.klo = (const uint64_t *)(d + o_klo); a.khi = (const uint64_t *)(d + o_khi); a.cnt = (uint32_t *)(d + o_cnt);
     uint64_t *d_base = (uint64_t *)(d + o_base);
     ScArgs c{};
@@ -503,4 +506,10 @@ extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radiu
     if (nomem_sort) return e->fail(HX_E_NOMEM, "one query's hits exceed HX_RANGE_SCRATCH (ordered by distance)");
     if (!count_only && *total_out > cap) return e->fail(HX_E_NOMEM, "capacity exceeded");
     return HX_OK;
+}
+
+extern "C" int hx_exact_range(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+                              const uint64_t *row_pass, int order, uint64_t cap, uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
+{
+    return hx_exact_range_src(e, op, cmp, radius, first_query, nq, first_row, n_rows, row_pass, nullptr, order, cap, offsets_out, ids_out, dist_out, total_out);
 }

@@ -278,18 +278,12 @@ hipError_t rgg_scan(hx_engine *e, int op, const RgGArgs &a, uint32_t Q, uint32_t
     }
 }
 
-} // namespace
-
-// =================================================================================================
-// C ABI
-// =================================================================================================
-extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
-                                       uint64_t first_row, uint64_t n_rows,
-                                       uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
-                                       int order, uint64_t cap,
-                                       uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
+// The body of hx_exact_range_filtered and hx_exact_range_set.  The filter source is host bitmaps (filters; set == nullptr) or the resident lists of a
+// filter set (set; filters unused): then the counts are the set's offsets, nothing is uploaded or compacted and the set's id array is the id base.
+int rgf_run(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq, uint64_t first_row, uint64_t n_rows,
+            uint32_t n_filters, const uint64_t *const *filters, const hx_filterset *set, const int32_t *filter_of, int order, uint64_t cap,
+            uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
 {
-    if (!e) return HX_E_ARG;
     const bool bit = e->dtype == HX_BIT;
     if (op < HX_OP_L2 || op > HX_OP_JACCARD || bit != (op == HX_OP_HAMMING || op == HX_OP_JACCARD))
         return e->fail(HX_E_ARG, "operator is not defined for this column type");
@@ -301,8 +295,17 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
     if (nq > 0 && !radius) return e->fail(HX_E_ARG, "NULL radius");
     if (!offsets_out || !total_out) return e->fail(HX_E_ARG, "NULL offsets or total output");
     if (!ids_out && dist_out) return e->fail(HX_E_ARG, "values without ids");
-    if (n_filters > HX_EXACT_MAX_FILTERS) return e->fail(HX_E_ARG, "more than HX_EXACT_MAX_FILTERS filters");
-    if (n_filters > 0 && !filters) return e->fail(HX_E_ARG, "NULL filters with n_filters > 0");
+    std::vector<int32_t> local_of; uint32_t set_f[HX_EXACT_MAX_FILTERS];   // a set: the call's distinct filters stand for the bitmaps
+    if (set) {
+        const int rc = hx_filterset_localize(e, set, nq, filter_of, local_of, set_f, &n_filters);
+        if (rc) return rc;
+        if (filter_of) filter_of = local_of.data();
+    } else {
+        if (n_filters > HX_EXACT_MAX_FILTERS) return e->fail(HX_E_ARG, "more than HX_EXACT_MAX_FILTERS filters");
+        if (n_filters > 0 && !filters) return e->fail(HX_E_ARG, "NULL filters with n_filters > 0");
+    }
+    auto set_off = [&](uint32_t v) { return set->off[set_f[v - 1]]; };
+    auto set_cnt = [&](uint32_t v) { return set->off[(size_t)set_f[v - 1] + 1] - set->off[set_f[v - 1]]; };
     // group v + 1 holds the queries of filter v (v = -1: no filter)
     uint32_t g_nq[HX_EXACT_MAX_FILTERS + 1] = {};
     if (!filter_of) g_nq[0] = nq;
@@ -310,13 +313,15 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
         for (uint32_t i = 0; i < nq; i++) {
             const int32_t f = filter_of[i];
             if (f < -1 || f >= (int32_t)n_filters) return e->fail(HX_E_ARG, "filter_of entry outside [-1, n_filters)");
-            if (f >= 0 && !filters[f]) return e->fail(HX_E_ARG, "a query references a NULL filter");
+            if (f >= 0 && !set && !filters[f]) return e->fail(HX_E_ARG, "a query references a NULL filter");
             g_nq[f + 1]++;
         }
     for (uint32_t v = 0; v <= n_filters; v++)                  // one distinct filter (or no query): this is hx_exact_range with that bitmap
-        if (g_nq[v] == nq)
-            return hx_exact_range(e, op, cmp, radius, first_query, nq, first_row, n_rows, v ? filters[v - 1] : nullptr, order, cap, offsets_out, ids_out,
-                                  dist_out, total_out);
+        if (g_nq[v] == nq) {
+            const HxIdList one{set && v ? set->d_ids + set_off(v) : nullptr, set && v ? set_cnt(v) : 0};
+            return hx_exact_range_src(e, op, cmp, radius, first_query, nq, first_row, n_rows, v && !set ? filters[v - 1] : nullptr, v && set ? &one : nullptr,
+                                      order, cap, offsets_out, ids_out, dist_out, total_out);
+        }
     const bool count_only = !ids_out, by_dist = order == HX_RANGE_BY_DISTANCE;
     const bool need_key = !count_only && (dist_out || by_dist);
     offsets_out[0] = 0; *total_out = 0;
@@ -334,7 +339,8 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
     for (uint32_t v = 0; v <= n_filters; v++) {
         g_idx[v] = -1;
         if (!g_nq[v]) continue;
-        if (v > 0) {
+        if (v > 0 && set) g_pass[v] = set_cnt(v);
+        else if (v > 0) {
             const uint64_t *words = filters[v - 1];
             woff.resize((size_t)(n_ref + 1) * n_words);
             uint32_t *wo = woff.data() + (size_t)n_ref * n_words;
@@ -351,8 +357,8 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
         }
         if (!g_pass[v]) continue;
         g_idx[v] = (int32_t)groups.size();
-        groups.push_back(RgGroup{g_pass[v], v ? total_ids : RG_NO_IDS, sc_legal && sc_enabled(g_pass[v], SC_MIN_ROWS_RANGE)});
-        if (v) total_ids += g_pass[v];
+        groups.push_back(RgGroup{g_pass[v], !v ? RG_NO_IDS : set ? set_off(v) : total_ids, sc_legal && sc_enabled(g_pass[v], SC_MIN_ROWS_RANGE)});
+        if (v && !set) total_ids += g_pass[v];
     }
     std::vector<int32_t> group_of(nq);
     for (uint32_t i = 0; i < nq; i++) {
@@ -425,7 +431,7 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
 
     RgGArgs a{};
     a.rows = e->d_rows; a.queries = e->d_queries; a.pitch = pitch; a.cap_sp = (uint32_t)std::min(e->dim, HX_SPARSE_MAX_NNZ);
-    a.ids = (const uint32_t *)d; a.row0 = (uint32_t)first_row;
+    a.ids = set ? set->d_ids : (const uint32_t *)d; a.row0 = (uint32_t)first_row;
     a.slots = (const uint32_t *)(d + o_slots); a.qseg = (const uint32_t *)(d + o_qseg);
     a.klo = (const uint64_t *)(d + o_klo); a.khi = (const uint64_t *)(d + o_khi); a.cnt = (uint32_t *)(d + o_cnt);
     uint64_t *d_base = (uint64_t *)(d + o_base);
@@ -553,4 +559,39 @@ extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const doub
     if (nomem_sort) return e->fail(HX_E_NOMEM, "one query's hits exceed HX_RANGE_SCRATCH (ordered by distance)");
     if (!count_only && *total_out > cap) return e->fail(HX_E_NOMEM, "capacity exceeded");
     return HX_OK;
+}
+
+} // namespace
+
+hipError_t hx_range_compact_lists(hx_engine *e, const uint64_t *d_words, const uint32_t *d_woff, uint64_t n_words, uint64_t n_rows, uint32_t row0,
+                                  uint32_t *out, const uint64_t *base, uint32_t n)
+{
+    RgCompactBases b{};
+    for (uint32_t i = 0; i < n && i < HX_EXACT_MAX_FILTERS; i++) b.base[i] = base[i];
+    hipLaunchKernelGGL(k_range_compact_g, dim3((uint32_t)((n_words + 255) / 256), std::min<uint32_t>(n, HX_EXACT_MAX_FILTERS)), dim3(256), 0, e->stream, d_words, d_woff,
+                       n_words, n_rows, row0, out, b);
+    return hipGetLastError();
+}
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" int hx_exact_range_filtered(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
+                                       uint64_t first_row, uint64_t n_rows,
+                                       uint32_t n_filters, const uint64_t *const *filters, const int32_t *filter_of,
+                                       int order, uint64_t cap,
+                                       uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
+{
+    if (!e) return HX_E_ARG;
+    return rgf_run(e, op, cmp, radius, first_query, nq, first_row, n_rows, n_filters, filters, nullptr, filter_of, order, cap, offsets_out, ids_out, dist_out,
+                   total_out);
+}
+
+extern "C" int hx_exact_range_set(hx_engine *e, int op, int cmp, const double *radius, uint32_t first_query, uint32_t nq,
+                                  const hx_filterset *s, const int32_t *filter_of, int order, uint64_t cap,
+                                  uint64_t *offsets_out, uint32_t *ids_out, double *dist_out, uint64_t *total_out)
+{
+    if (!e) return HX_E_ARG;
+    if (const int rc = hx_filterset_usable(e, s)) return rc;
+    return rgf_run(e, op, cmp, radius, first_query, nq, s->first_row, s->n_rows, 0, nullptr, s, filter_of, order, cap, offsets_out, ids_out, dist_out, total_out);
 }
