@@ -191,6 +191,15 @@ struct Graph {
     const Cand *list(uint32_t e, int layer) const { return const_cast<Graph *>(this)->list(e, layer); }
     uint16_t &cnt(uint32_t e, int layer) { return layer == 0 ? n0_cnt[e] : up_cnt[upc_off[e] + (layer - 1)]; }
     uint16_t cnt(uint32_t e, int layer) const { return const_cast<Graph *>(this)->cnt(e, layer); }
+    // overwrites a list with c neighbours given as flat (id, distance) arrays, or with the first c (default: all) of v
+    void store(uint32_t e, int layer, const uint32_t *ids, const float *d, uint32_t c)
+    {
+        Cand *l = list(e, layer);
+        for (uint32_t k = 0; k < c; k++) l[k] = Cand{d[k], ids[k]};
+        cnt(e, layer) = (uint16_t)c;
+    }
+    void store(uint32_t e, int layer, const std::vector<Cand> &v, size_t c) { std::copy_n(v.begin(), c, list(e, layer)); cnt(e, layer) = (uint16_t)c; }
+    void store(uint32_t e, int layer, const std::vector<Cand> &v) { store(e, layer, v, v.size()); }
 };
 
 static void stable_sort_asc(std::vector<Cand> &v) { std::stable_sort(v.begin(), v.end(), [](const Cand &a, const Cand &b) { return a.d < b.d; }); }
@@ -422,9 +431,6 @@ struct InsertTask : LsTask {
     std::vector<Cand> ep, w;
     SearchCore sc; SelectTask sel;
     std::vector<std::vector<Cand>> nb;     // selected neighbours per layer 0..new_level
-    // the layers' result sets W (ascending) when the traversal kernel has already searched (MODE 3: m > 32, whose select and back-links the device
-    // kernels do not serve): the task then only runs select_neighbors per layer
-    std::vector<std::vector<Cand>> preset; bool has_preset = false;
 
     bool post_search() { dist_ids = sc.pend; q_sel = id; n_dist += dist_ids.size(); return true; }
     bool advance(const float *dres, const float *pres) override
@@ -434,12 +440,6 @@ struct InsertTask : LsTask {
             switch (st) {
             case S_INIT:
                 nb.assign(new_level + 1, {});
-                if (has_preset) {                                                    // mod.rs:403-427 with W given
-                    lc = std::min(new_level, entry_level);
-                    if (lc < 0) { st = S_DONE; break; }
-                    w = preset[lc]; sel.start(&w, (size_t)g->lm(lc)); st = S_SELECT; pres = nullptr;
-                    break;
-                }
                 dist_ids.push_back(entry); q_sel = id; n_dist += 1; st = S_ENTRY;    // mod.rs:371-377
                 return true;
             case S_ENTRY:
@@ -472,12 +472,6 @@ struct InsertTask : LsTask {
             case S_SELECT:                                                           // mod.rs:419-425
                 { const float *pp = pres; pres = nullptr; if (sel.step(pp, *this)) return true; }
                 nb[lc] = sel.R;
-                if (has_preset) {
-                    lc--;
-                    if (lc < 0) { st = S_DONE; break; }
-                    w = preset[lc]; sel.start(&w, (size_t)g->lm(lc)); pres = nullptr;
-                    break;
-                }
                 ep = w;
                 lc--;
                 st = S_SEARCH;
@@ -1049,6 +1043,79 @@ struct hx_index {
         pool->set_hot(false);
         return rc;
     }
+
+    // What every traversal-kernel site does with the statuses of its first launch (roomy = 1; `first`, n tasks): a task that reported 0 is accepted --
+    // accept(task, src, results), src = the task's index in the launch whose results these are; first_accepted: the caller has done that already, under
+    // parallel_for -- the tasks whose tables overflowed (FS_OVERFLOW, status 1) get one more try on the device with roomier tables: relaunch(again, second)
+    // launches them with roomy = 8, and they are accepted from `second`.  What fails otherwise, or again, is appended to `todo` (empty on entry) for the
+    // lock-step driver: the first launch's in task order, then the relaunch's.
+    template <class R, class Accept, class Relaunch>
+    int retry_ladder(uint32_t n, const R &first, bool first_accepted, Accept accept, Relaunch relaunch, std::vector<uint32_t> &todo)
+    {
+        std::vector<uint32_t> again;
+        for (uint32_t t = 0; t < n; t++) { if (first.status[t] == 1) again.push_back(t); else if (first.status[t] != 0) todo.push_back(t); else if (!first_accepted) accept(t, t, first); }
+        if (!again.empty()) {
+            R second;
+            int rc = relaunch(again, second);
+            if (rc) return rc;
+            for (uint32_t k = 0; k < (uint32_t)again.size(); k++) { if (second.status[k] != 0) todo.push_back(again[k]); else accept(again[k], k, second); }
+        }
+        fused_tasks += n; fused_redo += todo.size();
+        return HX_OK;
+    }
+
+    // find_element_neighbors on the lock-step driver for members of the open batch (element id = id0 + member): arms an InsertTask per member, runs
+    // them, adds their counters and hands each finished task (nb[lc]: the selected neighbours per layer) to sink(member, task)
+    template <class Sink> int lockstep_insert(const std::vector<uint32_t> &members, uint32_t id0, Sink sink)
+    {
+        std::vector<std::unique_ptr<InsertTask>> &its = insert_pool;
+        while (its.size() < members.size()) its.emplace_back(new InsertTask());
+        std::vector<LsTask *> tasks(members.size());
+        for (size_t ti = 0; ti < members.size(); ti++) {
+            InsertTask &t = *its[ti];
+            t.st = InsertTask::S_INIT; t.lc = 0; t.n_dist = t.n_pair = 0; t.clear_req();
+            t.g = &g; t.id = id0 + members[ti]; t.new_level = g.level[t.id]; t.entry = bs.entry; t.entry_level = bs.entry_level; t.efc = efc;
+            if (mfma_on()) { int rcn = e->mfma_norms(e->n_rows); if (rcn) return fail(rcn, e->err); }
+            arm_select(t.sel);
+            tasks[ti] = &t;
+        }
+        int rc = run_lockstep(tasks);
+        if (rc) return rc;
+        for (size_t ti = 0; ti < members.size(); ti++) {
+            InsertTask &t = *its[ti];
+            counters[1] += t.n_dist; counters[2] += t.n_pair;
+            mfma_pairs += t.sel.n_mfma; mfma_exact += t.sel.n_exact;
+            if ((rc = sink(members[ti], t))) return rc;
+        }
+        return HX_OK;
+    }
+
+    // k_fused MODE 3, "search only, W lists out": per task the greedy descent and a search_layer per layer 0..min(tl[t], its entry's level); layer lc of task t is
+    // problem prob[t] + lc of P, its sorted result set W stays on the device at wsel.d_wl + problem * wstride (|W| in wsel.d_cnt) and, when wcnt / wl are given,
+    // is read back into them.  ondisk: search_layer_disk semantics (aminsert); h_entry / d_skip: the per-task entry points and the skip set of vacuum's
+    // repair searches.  tstat: the tasks' statuses (non-zero: outgrew its tables, the caller's lock-step driver; counted here), cnts as fused_run returns
+    // them; `what` prefixes the error strings.
+    int search_w(const char *what, uint32_t n, const uint32_t *qsel, const int32_t *tl, const uint32_t *prob, uint32_t P, uint32_t ef, uint32_t wstride,
+                 uint32_t entry, int entry_level, bool ondisk, const uint32_t *h_entry, const uint8_t *d_skip, uint32_t *tstat, uint64_t cnts[2],
+                 std::vector<uint32_t> *wcnt = nullptr, std::vector<uint2> *wl = nullptr)
+    {
+        int rc;
+        if ((rc = e->wsel_reserve(P, wstride)) || (rc = e->db_reserve_records(n))) return fail(rc, e->err);
+        HxWselWork &w = e->wsel;
+        if (hipMemsetAsync(w.d_cnt, 0, (size_t)P * 4, e->stream) != hipSuccess) return fail(HX_E_HIP, std::string(what) + "clearing the W counts failed");
+        HxFusedDev dev; dev.d_rec = e->bw.d_rec; dev.rec_words = hx_rec_words((uint32_t)g.m); dev.h_slots = nullptr;
+        dev.d_wl_out = w.d_wl; dev.d_wl_cnt = w.d_cnt; dev.h_prob = prob; dev.ondisk = ondisk; dev.h_entry = h_entry; dev.d_skip = d_skip;
+        const double t0 = now_s();
+        if ((rc = e->fused_run(3, n, qsel, tl, ef, 0, entry, entry_level, nullptr, nullptr, nullptr, tstat, cnts, nullptr, nullptr, 1, &dev))) return fail(rc, e->err);
+        prof[6] += now_s() - t0;
+        fused_tasks += n; for (uint32_t i = 0; i < n; i++) fused_redo += tstat[i] != 0;
+        if (!wcnt) return HX_OK;
+        wcnt->resize(P); wl->resize((size_t)P * wstride);
+        if (hipMemcpyAsync(wcnt->data(), w.d_cnt, (size_t)P * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipMemcpyAsync(wl->data(), w.d_wl, (size_t)P * wstride * 8, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) return fail(HX_E_HIP, std::string(what) + "reading the W lists failed");
+        return HX_OK;
+    }
 };
 
 // types/hnsw.rs:337-349 with BLCKSZ 8192: (8192 - 24 - 8 - 4 - 4) / 6 / m - 2, capped at 255
@@ -1121,11 +1188,11 @@ int hx_index_batch_search(hx_index *ix, uint32_t lo, uint32_t hi)
     hx_index::Timer t_bs(ix->prof[11]);
     BatchState &bs = ix->bs; Graph &g = ix->g;
     if (!bs.open || lo > hi || hi > bs.b) return ix->fail(HX_E_STATE, "no open batch / bad member range");
-    std::vector<uint32_t> todo;                                  // batch members still to be searched by the lock-step path
+    const uint32_t n = hi - lo, lm0 = 2u * (uint32_t)g.m;
+    std::vector<uint32_t> todo;                                  // batch members (counted from lo) still to be searched by the lock-step path
     if (ix->fused_ok() && hi > lo) {
         int rc = ix->sync_mirror();
         if (rc) return rc;
-        const uint32_t n = hi - lo, lm0 = 2u * (uint32_t)g.m;
         std::vector<uint32_t> qsel(n); std::vector<int32_t> tl(n);
         for (uint32_t i = 0; i < n; i++) { qsel[i] = bs.base + lo + i; tl[i] = g.level[bs.base + lo + i]; }
         uint64_t cnts[2] = {0, 0};
@@ -1135,168 +1202,73 @@ int hx_index_batch_search(hx_index *ix, uint32_t lo, uint32_t hi)
                                    nullptr, nullptr, nullptr, nullptr, cnts, nullptr, &v))) return ix->fail(rc, ix->e->err);
         ix->prof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
-        const uint32_t *status = v.status, *ocnt = v.cnt, *oids = v.ids; const float *od = v.d;
+        auto take = [&](uint32_t i, size_t src, const HxFusedView &r) {
+            const uint32_t id = bs.base + lo + i;
+            for (int lc = 0; lc <= g.level[id]; lc++) {
+                const size_t ob = (src * HX_FUSED_MAXL + lc) * lm0;
+                g.store(id, lc, r.ids + ob, r.d + ob, r.cnt[src * HX_FUSED_MAXL + lc]);
+            }
+            bs.searched[lo + i] = 1;
+        };
         ix->pool->parallel_for((n + 511) / 512, [&](size_t ci) {
-            for (uint32_t i = (uint32_t)ci * 512; i < std::min<uint32_t>(n, (uint32_t)ci * 512 + 512); i++) {
-                const uint32_t id = bs.base + lo + i;
-                if (status[i] != 0) continue;
-                for (int lc = 0; lc <= g.level[id]; lc++) {
-                    const uint32_t c = ocnt[(size_t)i * HX_FUSED_MAXL + lc]; Cand *lst = g.list(id, lc);
-                    const size_t ob = ((size_t)i * HX_FUSED_MAXL + lc) * lm0;
-                    for (uint32_t k = 0; k < c; k++) lst[k] = Cand{od[ob + k], oids[ob + k]};
-                    g.cnt(id, lc) = (uint16_t)c;
-                }
-                bs.searched[lo + i] = 1;
-            }
+            for (uint32_t i = (uint32_t)ci * 512; i < std::min<uint32_t>(n, (uint32_t)ci * 512 + 512); i++) if (v.status[i] == 0) take(i, i, v);
         });
-        std::vector<uint32_t> again;                             // members whose tables overflowed: one more try on the device with roomier tables
-        for (uint32_t i = 0; i < n; i++) { if (status[i] == 0) ix->mark_dirty(bs.base + lo + i); else if (status[i] == 1) again.push_back(lo + i); else todo.push_back(lo + i); }
-        if (!again.empty()) {
-            const uint32_t na = (uint32_t)again.size();
-            std::vector<uint32_t> q2(na); std::vector<int32_t> l2(na);
-            for (uint32_t k = 0; k < na; k++) { q2[k] = bs.base + again[k]; l2[k] = g.level[bs.base + again[k]]; }
-            HxFusedView v2;
-            if ((rc = ix->e->fused_run(1, na, q2.data(), l2.data(), (uint32_t)ix->efc, 0, bs.entry, bs.entry_level,
-                                       nullptr, nullptr, nullptr, nullptr, cnts, nullptr, &v2, 8))) return ix->fail(rc, ix->e->err);
-            ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
-            for (uint32_t k = 0; k < na; k++) {
-                const uint32_t id = bs.base + again[k];
-                if (v2.status[k] != 0) { todo.push_back(again[k]); continue; }
-                for (int lc = 0; lc <= g.level[id]; lc++) {
-                    const uint32_t c = v2.cnt[(size_t)k * HX_FUSED_MAXL + lc]; Cand *lst = g.list(id, lc);
-                    const size_t ob = ((size_t)k * HX_FUSED_MAXL + lc) * lm0;
-                    for (uint32_t j = 0; j < c; j++) lst[j] = Cand{v2.d[ob + j], v2.ids[ob + j]};
-                    g.cnt(id, lc) = (uint16_t)c;
-                }
-                ix->mark_dirty(id);
-                bs.searched[again[k]] = 1;
-            }
-        }
-        ix->fused_tasks += n; ix->fused_redo += todo.size();
-        if (todo.empty()) return HX_OK;
+        for (uint32_t i = 0; i < n; i++) if (v.status[i] == 0) ix->mark_dirty(bs.base + lo + i);
+        rc = ix->retry_ladder(n, v, true, [&](uint32_t i, size_t src, const HxFusedView &r) { take(i, src, r); ix->mark_dirty(bs.base + lo + i); },
+            [&](const std::vector<uint32_t> &again, HxFusedView &v2) -> int {
+                const uint32_t na = (uint32_t)again.size();
+                std::vector<uint32_t> q2(na); std::vector<int32_t> l2(na);
+                for (uint32_t k = 0; k < na; k++) { q2[k] = bs.base + lo + again[k]; l2[k] = g.level[bs.base + lo + again[k]]; }
+                int r = ix->e->fused_run(1, na, q2.data(), l2.data(), (uint32_t)ix->efc, 0, bs.entry, bs.entry_level,
+                                         nullptr, nullptr, nullptr, nullptr, cnts, nullptr, &v2, 8);
+                if (r) return ix->fail(r, ix->e->err);
+                ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
+                return HX_OK;
+            }, todo);
+        if (rc) return rc;
     } else if (ix->fused && (2 * g.m > 64 || ix->e->dtype == HX_SPARSE) && ix->e->pitch <= 8192 && hi > lo) {
         // m > 32 (the reference allows m <= 100, options.rs:203-225) and sparsevec rows: the insert-mode select and the back-link kernels are built for lists of
         // <= 64 and for dense rows, but
         // the searches -- the bulk of the distance evaluations -- run in the traversal kernel all the same (MODE 3 walks lists longer than a wavefront
-        // 64 ids at a time and hands out every layer's W); select_neighbors and update_neighbor_connections follow on the lock-step driver.
+        // 64 ids at a time and hands out every layer's W); select_neighbors and update_neighbor_connections follow in hx_biglist.hip's list kernels.
         int rc = ix->sync_mirror();
         if (rc) return rc;
         hx_engine *e = ix->e;
-        const uint32_t n = hi - lo;
         std::vector<uint32_t> qsel(n), prob(n), tstat(n); std::vector<int32_t> tl(n);
         uint32_t P = 0;
         for (uint32_t i = 0; i < n; i++) { qsel[i] = bs.base + lo + i; tl[i] = g.level[bs.base + lo + i]; prob[i] = P; P += (uint32_t)std::min(tl[i], bs.entry_level) + 1u; }
-        if ((rc = e->wsel_reserve(P, (uint32_t)ix->efc)) || (rc = e->db_reserve_records(n))) return ix->fail(rc, e->err);
-        HxWselWork &w = e->wsel;
-        if (hipMemsetAsync(w.d_cnt, 0, (size_t)P * 4, e->stream) != hipSuccess) return ix->fail(HX_E_HIP, "clearing the W counts failed");
-        HxFusedDev dev; dev.d_rec = e->bw.d_rec; dev.rec_words = hx_rec_words((uint32_t)g.m); dev.h_slots = nullptr;
-        dev.d_wl_out = w.d_wl; dev.d_wl_cnt = w.d_cnt; dev.h_prob = prob.data();
         uint64_t cnts[2] = {0, 0};
-        const double t0 = hx_index::now_s();
-        if ((rc = e->fused_run(3, n, qsel.data(), tl.data(), (uint32_t)ix->efc, 0, bs.entry, bs.entry_level,
-                               nullptr, nullptr, nullptr, tstat.data(), cnts, nullptr, nullptr, 1, &dev))) return ix->fail(rc, e->err);
-        ix->prof[6] += hx_index::now_s() - t0;
+        if ((rc = ix->search_w("", n, qsel.data(), tl.data(), prob.data(), P, (uint32_t)ix->efc, (uint32_t)ix->efc, bs.entry, bs.entry_level,
+                               false, nullptr, nullptr, tstat.data(), cnts))) return rc;
         ix->counters[1] += cnts[0];
-        static const bool biglist_off = getenv("HX_BIGLIST") && atoi(getenv("HX_BIGLIST")) == 0;     // experiments: select / back-links of these shapes on the lock-step driver
-        if (!biglist_off) {
-            // select_neighbors per (member, layer) in k_select_w (hx_biglist.hip), straight from the result sets the traversal kernel left on the device
-            const uint32_t lm0 = 2u * (uint32_t)g.m;
-            std::vector<uint32_t> lmv(P, lm0);
-            for (uint32_t i = 0; i < n; i++) for (int lc = 0; lc <= std::min(tl[i], bs.entry_level); lc++) lmv[prob[i] + (uint32_t)lc] = (uint32_t)g.lm(lc);
-            const uint32_t *oids = nullptr, *ocnt = nullptr; const float *od = nullptr; uint64_t np = 0;
-            if ((rc = e->biglist_select(P, (uint32_t)ix->efc, lmv.data(), lm0, &oids, &od, &ocnt, &np))) return ix->fail(rc, e->err);
-            ix->counters[2] += np;
-            ix->pool->parallel_for((n + 255) / 256, [&](size_t ci) {
-                for (uint32_t i = (uint32_t)ci * 256; i < std::min<uint32_t>(n, (uint32_t)ci * 256 + 256); i++) {
-                    if (tstat[i] != 0) continue;
-                    const uint32_t id = bs.base + lo + i; const int start = std::min(tl[i], bs.entry_level);
-                    for (int lc = 0; lc <= tl[i]; lc++) {
-                        Cand *lst = g.list(id, lc); uint32_t c = 0;
-                        if (lc <= start) {
-                            const size_t pr = (size_t)prob[i] + (size_t)lc; c = std::min<uint32_t>(ocnt[pr], (uint32_t)g.lm(lc));
-                            for (uint32_t k = 0; k < c; k++) lst[k] = Cand{od[pr * lm0 + k], oids[pr * lm0 + k]};
-                        }
-                        g.cnt(id, lc) = (uint16_t)c;
-                    }
-                    bs.searched[lo + i] = 1;
+        // select_neighbors per (member, layer) in k_select_w (hx_biglist.hip), straight from the result sets the traversal kernel left on the device
+        std::vector<uint32_t> lmv(P, lm0);
+        for (uint32_t i = 0; i < n; i++) for (int lc = 0; lc <= std::min(tl[i], bs.entry_level); lc++) lmv[prob[i] + (uint32_t)lc] = (uint32_t)g.lm(lc);
+        const uint32_t *oids = nullptr, *ocnt = nullptr; const float *od = nullptr; uint64_t np = 0;
+        if ((rc = e->biglist_select(P, (uint32_t)ix->efc, lmv.data(), lm0, &oids, &od, &ocnt, &np))) return ix->fail(rc, e->err);
+        ix->counters[2] += np;
+        ix->pool->parallel_for((n + 255) / 256, [&](size_t ci) {
+            for (uint32_t i = (uint32_t)ci * 256; i < std::min<uint32_t>(n, (uint32_t)ci * 256 + 256); i++) {
+                if (tstat[i] != 0) continue;
+                const uint32_t id = bs.base + lo + i; const int start = std::min(tl[i], bs.entry_level);
+                for (int lc = 0; lc <= tl[i]; lc++) {
+                    if (lc > start) { g.cnt(id, lc) = 0; continue; }
+                    const size_t pr = (size_t)prob[i] + (size_t)lc;
+                    g.store(id, lc, oids + pr * lm0, od + pr * lm0, std::min<uint32_t>(ocnt[pr], (uint32_t)g.lm(lc)));
                 }
-            });
-            for (uint32_t i = 0; i < n; i++) { if (tstat[i] != 0) todo.push_back(lo + i); else ix->mark_dirty(bs.base + lo + i); }
-            ix->fused_tasks += n; ix->fused_redo += todo.size();
-            if (todo.empty()) return HX_OK;
-        } else {
-        std::vector<uint32_t> wcnt(P); std::vector<uint2> wl((size_t)P * ix->efc);
-        if (hipMemcpyAsync(wcnt.data(), w.d_cnt, (size_t)P * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipMemcpyAsync(wl.data(), w.d_wl, (size_t)P * ix->efc * 8, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess) return ix->fail(HX_E_HIP, "reading the W lists failed");
-        std::vector<std::unique_ptr<InsertTask>> &its = ix->insert_pool;
-        while (its.size() < n) its.emplace_back(new InsertTask());
-        std::vector<LsTask *> tasks; std::vector<uint32_t> members;
-        for (uint32_t i = 0; i < n; i++) {
-            if (tstat[i] != 0) { todo.push_back(lo + i); continue; }
-            InsertTask &t = *its[tasks.size()];
-            t.st = InsertTask::S_INIT; t.lc = 0; t.n_dist = t.n_pair = 0; t.clear_req();
-            t.g = &g; t.id = bs.base + lo + i; t.new_level = tl[i]; t.entry = bs.entry; t.entry_level = bs.entry_level; t.efc = ix->efc;
-            const int start = std::min(tl[i], bs.entry_level);
-            t.preset.assign(start + 1, {}); t.has_preset = true;
-            for (int lc = 0; lc <= start; lc++) {
-                const size_t pr = (size_t)prob[i] + (size_t)lc; const uint2 *W = wl.data() + pr * ix->efc;
-                t.preset[lc].resize(wcnt[pr]);
-                for (uint32_t k = 0; k < wcnt[pr]; k++) { memcpy(&t.preset[lc][k].d, &W[k].x, 4); t.preset[lc][k].id = W[k].y; }
+                bs.searched[lo + i] = 1;
             }
-            if (ix->mfma_on()) { int rcn = e->mfma_norms(e->n_rows); if (rcn) return ix->fail(rcn, e->err); }
-            ix->arm_select(t.sel);
-            tasks.push_back(&t); members.push_back(lo + i);
-        }
-        if ((rc = ix->run_lockstep(tasks))) return rc;
-        for (size_t ti = 0; ti < tasks.size(); ti++) {
-            InsertTask &t = *its[ti];
-            for (int lc = 0; lc <= t.new_level; lc++) {
-                Cand *lst = g.list(t.id, lc);
-                for (size_t k = 0; k < t.nb[lc].size(); k++) lst[k] = t.nb[lc][k];
-                g.cnt(t.id, lc) = (uint16_t)t.nb[lc].size();
-            }
-            t.has_preset = false; t.preset.clear();
-            ix->counters[1] += t.n_dist; ix->counters[2] += t.n_pair;
-            ix->mfma_pairs += t.sel.n_mfma; ix->mfma_exact += t.sel.n_exact;
-            ix->mark_dirty(t.id);
-            bs.searched[members[ti]] = 1;
-        }
-        ix->fused_tasks += n; ix->fused_redo += todo.size();
-        if (todo.empty()) return HX_OK;
-        }
+        });
+        for (uint32_t i = 0; i < n; i++) { if (tstat[i] != 0) todo.push_back(i); else ix->mark_dirty(bs.base + lo + i); }
     } else {
-        for (uint32_t i = lo; i < hi; i++) todo.push_back(i);
+        for (uint32_t i = 0; i < n; i++) todo.push_back(i);
     }
-    std::vector<std::unique_ptr<InsertTask>> &its = ix->insert_pool;
-    while (its.size() < todo.size()) its.emplace_back(new InsertTask());
-    std::vector<LsTask *> tasks(todo.size());
-    for (size_t ti = 0; ti < todo.size(); ti++) {
-        const uint32_t i = todo[ti];
-        InsertTask &t = *its[ti];
-        t.has_preset = false;
-        t.st = InsertTask::S_INIT; t.lc = 0; t.n_dist = t.n_pair = 0; t.clear_req();
-        t.g = &g; t.id = bs.base + i; t.new_level = g.level[t.id]; t.entry = bs.entry; t.entry_level = bs.entry_level; t.efc = ix->efc;
-        if (ix->mfma_on()) { int rcn = ix->e->mfma_norms(ix->e->n_rows); if (rcn) return ix->fail(rcn, ix->e->err); }
-        ix->arm_select(t.sel);
-        tasks[ti] = &t;
-    }
-    int rc = ix->run_lockstep(tasks);
-    if (rc) return rc;
-    for (size_t ti = 0; ti < todo.size(); ti++) {               // elements[new_idx].neighbors[lc].items = neighbors (mod.rs:422)
-        const uint32_t i = todo[ti];
-        InsertTask &t = *its[ti];
-        for (int lc = 0; lc <= t.new_level; lc++) {
-            Cand *lst = g.list(t.id, lc);
-            for (size_t k = 0; k < t.nb[lc].size(); k++) lst[k] = t.nb[lc][k];
-            g.cnt(t.id, lc) = (uint16_t)t.nb[lc].size();
-        }
-        ix->counters[1] += t.n_dist; ix->counters[2] += t.n_pair;
-        ix->mfma_pairs += t.sel.n_mfma; ix->mfma_exact += t.sel.n_exact;
+    return ix->lockstep_insert(todo, bs.base + lo, [&](uint32_t i, const InsertTask &t) {   // elements[new_idx].neighbors[lc].items = neighbors (mod.rs:422)
+        for (int lc = 0; lc <= t.new_level; lc++) g.store(t.id, lc, t.nb[lc]);
         ix->mark_dirty(t.id);
-        bs.searched[i] = 1;
-    }
-    return HX_OK;
+        bs.searched[lo + i] = 1;
+        return HX_OK;
+    });
 }
 
 // serialized neighbour lists of the new members [lo, hi): per member, per layer 0..level: u32 count, lm x {u32 id, f32 d}
@@ -1484,17 +1456,14 @@ int hx_index_batch_links(hx_index *ix, uint32_t rank, uint32_t world)
             else
             ix->pool->parallel_for((ng + 2047) / 2048, [&](size_t ci) {
                 for (size_t gi = ci * 2048; gi < std::min<size_t>(ng, ci * 2048 + 2048); gi++) {
-                    Cand *lst = g.list(tg[gi], (int)ly[gi]); const uint32_t c = ocnt[gi];
-                    for (uint32_t k = 0; k < c; k++) lst[k] = Cand{odd[gi * lm0 + k], oids[gi * lm0 + k]};
-                    g.cnt(tg[gi], (int)ly[gi]) = (uint16_t)c;
+                    g.store(tg[gi], (int)ly[gi], oids + gi * lm0, odd + gi * lm0, ocnt[gi]);
                 }
             });
         }
         bs.linked = true;
         return HX_OK;
     }
-    static const bool biglist_off = getenv("HX_BIGLIST") && atoi(getenv("HX_BIGLIST")) == 0;
-    if (ix->fused && ix->e->pitch <= 8192 && !biglist_off) {
+    if (ix->fused && ix->e->pitch <= 8192) {
         // lists the lane-per-slot kernels do not serve (m > 32: up to 200 slots; sparsevec rows): k_list_ops (hx_biglist.hip), one wavefront per owned list, from the
         // list contents the host hands over; the new lists come back into the host copy (the master for these index shapes)
         auto &own = ix->ls.own; own.clear();
@@ -1527,9 +1496,7 @@ int hx_index_batch_links(hx_index *ix, uint32_t rank, uint32_t world)
                 for (size_t k = ci * 1024; k < std::min<size_t>(ng, ci * 1024 + 1024); k++) {
                     const auto &gr = bs.grp[own[k]];
                     const uint32_t t = ops[gr.first].target; const int ly = ops[gr.first].layer;
-                    Cand *lst = g.list(t, ly); const uint32_t c = std::min<uint32_t>(h_cnt[k], (uint32_t)g.lm(ly));
-                    for (uint32_t i = 0; i < c; i++) lst[i] = Cand{h_d[k * lm0 + i], h_ids[k * lm0 + i]};
-                    g.cnt(t, ly) = (uint16_t)c;
+                    g.store(t, ly, h_ids + k * lm0, h_d + k * lm0, std::min<uint32_t>(h_cnt[k], (uint32_t)g.lm(ly)));
                 }
             });
             for (uint32_t k = 0; k < ng; k++) ix->dirty.emplace_back(ops[bs.grp[own[k]].first].target, ops[bs.grp[own[k]].first].layer);
@@ -1726,39 +1693,27 @@ int hx_index_dbatch_search(hx_index *ix, uint32_t lo, uint32_t hi, void *d_recor
     for (uint32_t k = 0; k < n; k++) status[slots[k]] = tstat[k];
     ix->prof[6] += hx_index::now_s() - t0;
     ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
-    std::vector<uint32_t> again, todo;
-    for (uint32_t i = 0; i < n; i++) { if (status[i] == 0) bs.searched[lo + i] = 1; else if (status[i] == 1) again.push_back(i); else todo.push_back(i); }
-    if (!again.empty()) {                                        // overflowed tables: one more try on the device with roomier ones
-        const uint32_t na = (uint32_t)again.size();
-        std::vector<uint32_t> q2(na), st2(na); std::vector<int32_t> l2(na);
-        for (uint32_t k = 0; k < na; k++) { q2[k] = bs.base + lo + again[k]; l2[k] = g.level[bs.base + lo + again[k]]; }
-        HxFusedDev dev2 = dev; dev2.h_slots = again.data();
-        if ((rc = ix->e->fused_run(1, na, q2.data(), l2.data(), (uint32_t)ix->efc, 0, bs.entry, bs.entry_level,
-                                   nullptr, nullptr, nullptr, st2.data(), cnts, nullptr, nullptr, 8, &dev2))) return ix->fail(rc, ix->e->err);
-        ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
-        for (uint32_t k = 0; k < na; k++) { if (st2[k] == 0) bs.searched[lo + again[k]] = 1; else todo.push_back(again[k]); }
-    }
-    ix->fused_tasks += n; ix->fused_redo += todo.size();
-    if (todo.empty()) return HX_OK;
+    std::vector<uint32_t> todo, st2;
+    HxFusedView first; first.status = status.data();            // the members' lists are in their device records: only the statuses come back
+    rc = ix->retry_ladder(n, first, false, [&](uint32_t i, size_t, const HxFusedView &) { bs.searched[lo + i] = 1; },
+        [&](const std::vector<uint32_t> &again, HxFusedView &second) -> int {
+            const uint32_t na = (uint32_t)again.size();
+            std::vector<uint32_t> q2(na); std::vector<int32_t> l2(na);
+            for (uint32_t k = 0; k < na; k++) { q2[k] = bs.base + lo + again[k]; l2[k] = g.level[bs.base + lo + again[k]]; }
+            st2.resize(na); second.status = st2.data();
+            HxFusedDev dev2 = dev; dev2.h_slots = again.data();
+            int r = ix->e->fused_run(1, na, q2.data(), l2.data(), (uint32_t)ix->efc, 0, bs.entry, bs.entry_level,
+                                     nullptr, nullptr, nullptr, st2.data(), cnts, nullptr, nullptr, 8, &dev2);
+            if (r) return ix->fail(r, ix->e->err);
+            ix->counters[1] += cnts[0]; ix->counters[2] += cnts[1];
+            return HX_OK;
+        }, todo);
+    if (rc || todo.empty()) return rc;
     // still overflowing: the lock-step driver on the host copy of the graph as of the batch start (the mirror holds exactly that)
     ix->host_stale = true;
-    std::vector<std::unique_ptr<InsertTask>> &its = ix->insert_pool;
-    while (its.size() < todo.size()) its.emplace_back(new InsertTask());
-    std::vector<LsTask *> tasks(todo.size());
-    for (size_t ti = 0; ti < todo.size(); ti++) {
-        InsertTask &t = *its[ti];
-        t.has_preset = false;
-        t.st = InsertTask::S_INIT; t.lc = 0; t.n_dist = t.n_pair = 0; t.clear_req();
-        t.g = &g; t.id = bs.base + lo + todo[ti]; t.new_level = g.level[t.id]; t.entry = bs.entry; t.entry_level = bs.entry_level; t.efc = ix->efc;
-        if (ix->mfma_on()) { int rcn = ix->e->mfma_norms(ix->e->n_rows); if (rcn) return ix->fail(rcn, ix->e->err); }
-        ix->arm_select(t.sel);
-        tasks[ti] = &t;
-    }
-    if ((rc = ix->run_lockstep(tasks))) return rc;
     const uint32_t lm0 = 2u * (uint32_t)g.m;
     std::vector<uint32_t> src(HX_FUSED_MAXL + 2u * HX_FUSED_MAXL * lm0);
-    for (size_t ti = 0; ti < todo.size(); ti++) {
-        InsertTask &t = *its[ti];
+    return ix->lockstep_insert(todo, bs.base + lo, [&](uint32_t i, const InsertTask &t) {
         std::fill(src.begin(), src.end(), 0u);
         for (int lc = 0; lc <= t.new_level; lc++) {
             src[lc] = (uint32_t)t.nb[lc].size();
@@ -1767,11 +1722,11 @@ int hx_index_dbatch_search(hx_index *ix, uint32_t lo, uint32_t hi, void *d_recor
                 memcpy(&src[HX_FUSED_MAXL + HX_FUSED_MAXL * lm0 + (size_t)lc * lm0 + k], &t.nb[lc][k].d, 4);
             }
         }
-        if ((rc = ix->e->db_fill_record((uint32_t *)d_records, todo[ti], src.data()))) return ix->fail(rc, ix->e->err);
-        ix->counters[1] += t.n_dist; ix->counters[2] += t.n_pair;
-        bs.searched[lo + todo[ti]] = 1;
-    }
-    return HX_OK;
+        int r = ix->e->db_fill_record((uint32_t *)d_records, i, src.data());
+        if (r) return ix->fail(r, ix->e->err);
+        bs.searched[lo + i] = 1;
+        return (int)HX_OK;
+    });
 }
 
 // every rank: duplicate merge + entry point + the members' lists into the mirror; then update_neighbor_connections for the lists this rank owns.
@@ -1987,25 +1942,13 @@ int hx_index_insert_ondisk(hx_index *ix, uint64_t first_row, uint32_t n, const i
         std::vector<uint32_t> ls_members;                                            // members for the lock-step driver
         if (ix->fused_scan_ok() && !dead_reachable && b >= 1) {
             if ((rc = ix->sync_mirror())) return rc;
-            hx_engine *e = ix->e;
-            std::vector<uint32_t> qsel(b), prob(b), tstat(b); std::vector<int32_t> tl(b);
+            std::vector<uint32_t> qsel(b), prob(b), tstat(b), wcnt; std::vector<int32_t> tl(b); std::vector<uint2> wl;
             uint32_t P = 0;
             for (uint32_t i = 0; i < b; i++) { qsel[i] = base + i; tl[i] = mlv[i]; prob[i] = P; P += (uint32_t)std::min(mlv[i], entry_level) + 1u; }
-            if ((rc = e->wsel_reserve(P, (uint32_t)ix->efc)) || (rc = e->db_reserve_records(b))) return ix->fail(rc, e->err);
-            HxWselWork &w = e->wsel;
-            if (hipMemsetAsync(w.d_cnt, 0, (size_t)P * 4, e->stream) != hipSuccess) return ix->fail(HX_E_HIP, "on-disk insert: clearing the W counts failed");
-            HxFusedDev dev; dev.d_rec = e->bw.d_rec; dev.rec_words = hx_rec_words((uint32_t)g.m); dev.h_slots = nullptr;
-            dev.d_wl_out = w.d_wl; dev.d_wl_cnt = w.d_cnt; dev.h_prob = prob.data(); dev.ondisk = true;
             uint64_t cnts[2] = {0, 0};
-            const double t0 = hx_index::now_s();
-            if ((rc = e->fused_run(3, b, qsel.data(), tl.data(), (uint32_t)ix->efc, 0, entry, entry_level,
-                                   nullptr, nullptr, nullptr, tstat.data(), cnts, nullptr, nullptr, 1, &dev))) return ix->fail(rc, e->err);
-            ix->prof[6] += hx_index::now_s() - t0;
+            if ((rc = ix->search_w("on-disk insert: ", b, qsel.data(), tl.data(), prob.data(), P, (uint32_t)ix->efc, (uint32_t)ix->efc, entry, entry_level,
+                                   true, nullptr, nullptr, tstat.data(), cnts, &wcnt, &wl))) return rc;
             ix->counters[4] += cnts[0];
-            std::vector<uint32_t> wcnt(P); std::vector<uint2> wl((size_t)P * ix->efc);
-            if (hipMemcpyAsync(wcnt.data(), w.d_cnt, (size_t)P * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                hipMemcpyAsync(wl.data(), w.d_wl, (size_t)P * ix->efc * 8, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) return ix->fail(HX_E_HIP, "on-disk insert: reading the W lists failed");
             for (uint32_t i = 0; i < b; i++) {
                 if (tstat[i] != 0) { ls_members.push_back(i); continue; }
                 const int start = std::min(mlv[i], entry_level);
@@ -2016,7 +1959,6 @@ int hx_index_insert_ondisk(hx_index *ix, uint64_t first_row, uint32_t n, const i
                     for (size_t k = wcnt[pr]; k-- > 0 && out.size() < lm;) { Cand c; memcpy(&c.d, &W[k].x, 4); c.id = W[k].y; out.push_back(c); }   // filtered.iter().rev().take(lm), insert.rs:1111-1117
                 }
             }
-            ix->fused_tasks += b; ix->fused_redo += ls_members.size();
         } else {
             for (uint32_t i = 0; i < b; i++) ls_members.push_back(i);
         }
@@ -2061,11 +2003,7 @@ int hx_index_insert_ondisk(hx_index *ix, uint64_t first_row, uint32_t n, const i
                 if (elem_out) elem_out[done + i] = (uint32_t)dup;
                 continue;
             }
-            for (int lc = 0; lc <= mlv[i]; lc++) {                                  // the new element's neighbour tuple, insert.rs:1384-1410
-                Cand *lst = g.list(id, lc); const size_t c = std::min(nbs[i][lc].size(), (size_t)g.lm(lc));
-                for (size_t k = 0; k < c; k++) lst[k] = nbs[i][lc][k];
-                g.cnt(id, lc) = (uint16_t)c;
-            }
+            for (int lc = 0; lc <= mlv[i]; lc++) g.store(id, lc, nbs[i][lc], std::min(nbs[i][lc].size(), (size_t)g.lm(lc)));   // the new element's neighbour tuple, insert.rs:1384-1410
             g.tids[id][0] = tids[done + i]; g.ntids[id] = 1;
             ix->mark_dirty(id);
             for (int lc = mlv[i]; lc >= 0; lc--) {                                  // update_neighbors_on_disk insert.rs:883-958: one get_update_index per (neighbour, layer)
@@ -2121,9 +2059,7 @@ int hx_index_insert_ondisk(hx_index *ix, uint64_t first_row, uint32_t n, const i
                 ix->pool->parallel_for((nr + 1023) / 1024, [&](size_t ci) {
                     for (size_t k = ci * 1024; k < std::min<size_t>(nr, ci * 1024 + 1024); k++) {
                         const UOp &o0 = ops[order[runs[k].first]];
-                        Cand *lst = g.list(o0.nbr, o0.layer); const uint32_t c = std::min<uint32_t>(h_cnt[k], (uint32_t)g.lm(o0.layer));
-                        for (uint32_t i = 0; i < c; i++) lst[i] = Cand{h_d[k * stride + i], h_ids[k * stride + i]};
-                        g.cnt(o0.nbr, o0.layer) = (uint16_t)c;
+                        g.store(o0.nbr, o0.layer, h_ids + k * stride, h_d + k * stride, std::min<uint32_t>(h_cnt[k], (uint32_t)g.lm(o0.layer)));
                     }
                 });
                 for (uint32_t k = 0; k < nr; k++) ix->dirty.emplace_back(ops[order[runs[k].first]].nbr, ops[order[runs[k].first]].layer);
@@ -2256,21 +2192,11 @@ int hx_index_vacuum(hx_index *ix, const int64_t *dead_tids, uint64_t n_dead, uin
         if (who.empty()) return HX_OK;
         int r = ix->sync_mirror();
         if (r) return r;
-        hx_engine *en = ix->e;
         const uint32_t nt = (uint32_t)who.size(), ef = (uint32_t)ix->efc + 1u, wst = ef + 2u + 254u;     // insert.rs:1081-1086; wst: the W lists' stride (hx_fused.inc.h: wcap of a repair launch)
-        if ((r = en->wsel_reserve(P, wst)) || (r = en->db_reserve_records(nt))) return ix->fail(r, en->err);
-        HxWselWork &w = en->wsel;
-        if (hipMemsetAsync(w.d_cnt, 0, (size_t)P * 4, en->stream) != hipSuccess) return ix->fail(HX_E_HIP, "vacuum: clearing the W counts failed");
-        HxFusedDev dev; dev.d_rec = en->bw.d_rec; dev.rec_words = hx_rec_words((uint32_t)g.m); dev.h_slots = nullptr;
-        dev.d_wl_out = w.d_wl; dev.d_wl_cnt = w.d_cnt; dev.h_prob = prob.data(); dev.ondisk = true; dev.h_entry = h_entry.data(); dev.d_skip = d_skip;
-        std::vector<uint32_t> tstat(nt); uint64_t cnts[2] = {0, 0};
-        if ((r = en->fused_run(3, nt, qsel.data(), tl.data(), ef, 0, (uint32_t)h_entry[0], g.level[h_entry[0]],
-                               nullptr, nullptr, nullptr, tstat.data(), cnts, nullptr, nullptr, 1, &dev))) return ix->fail(r, en->err);
+        std::vector<uint32_t> tstat(nt), wcnt; std::vector<uint2> wl; uint64_t cnts[2] = {0, 0};
+        if ((r = ix->search_w("vacuum: ", nt, qsel.data(), tl.data(), prob.data(), P, ef, wst, (uint32_t)h_entry[0], g.level[h_entry[0]],
+                              true, h_entry.data(), d_skip, tstat.data(), cnts, &wcnt, &wl))) return r;
         ix->counters[4] += cnts[0];
-        std::vector<uint32_t> wcnt(P); std::vector<uint2> wl((size_t)P * wst);
-        if (hipMemcpyAsync(wcnt.data(), w.d_cnt, (size_t)P * 4, hipMemcpyDeviceToHost, en->stream) != hipSuccess ||
-            hipMemcpyAsync(wl.data(), w.d_wl, (size_t)P * wst * 8, hipMemcpyDeviceToHost, en->stream) != hipSuccess ||
-            hipStreamSynchronize(en->stream) != hipSuccess) return ix->fail(HX_E_HIP, "vacuum: reading the W lists failed");
         for (uint32_t k = 0; k < nt; k++) {
             const uint32_t e = who[k];
             if (tstat[k] != 0) { left.push_back(e); left_ent.push_back((int64_t)h_entry[k]); continue; }   // outgrew its tables: the lock-step driver
@@ -2288,7 +2214,6 @@ int hx_index_vacuum(hx_index *ix, const int64_t *dead_tids, uint64_t n_dead, uin
             }
             ix->mark_dirty(e); n_rep++;
         }
-        ix->fused_tasks += nt; ix->fused_redo += left.size();
         return HX_OK;
     };
     auto repair = [&](const std::vector<uint32_t> &elems_in, const std::vector<int64_t> &entries_in) -> int {
@@ -2316,11 +2241,7 @@ int hx_index_vacuum(hx_index *ix, const int64_t *dead_tids, uint64_t n_dead, uin
             DiskNeighborsTask &t = *static_cast<DiskNeighborsTask *>(tasks[i]);
             const uint32_t e = who[i];
             ix->counters[4] += t.n_dist;
-            for (int lc = 0; lc <= g.level[e]; lc++) {
-                Cand *lst = g.list(e, lc); const size_t c = lc < (int)t.nb.size() ? std::min(t.nb[lc].size(), (size_t)g.lm(lc)) : 0;
-                for (size_t k = 0; k < c; k++) lst[k] = t.nb[lc][k];
-                g.cnt(e, lc) = (uint16_t)c;
-            }
+            for (int lc = 0; lc <= g.level[e]; lc++) { if (lc < (int)t.nb.size()) g.store(e, lc, t.nb[lc], std::min(t.nb[lc].size(), (size_t)g.lm(lc))); else g.cnt(e, lc) = 0; }
             ix->mark_dirty(e);
             n_rep++;
         }
@@ -2472,9 +2393,7 @@ int hx_index_set_neighbors(hx_index *ix, uint32_t elem, int layer, uint32_t coun
     if (!ix || elem >= ix->g.size()) return HX_E_ARG;
     Graph &g = ix->g;
     if (layer < 0 || g.level[elem] < layer || count > (uint32_t)g.lm(layer) || (count && (!ids || !dist))) return ix->fail(HX_E_ARG, "bad neighbour list");
-    Cand *l = g.list(elem, layer);
-    for (uint32_t k = 0; k < count; k++) l[k] = Cand{dist[k], ids[k]};
-    g.cnt(elem, layer) = (uint16_t)count;
+    g.store(elem, layer, ids, dist, count);
     ix->dirty.emplace_back(elem, layer);
     return HX_OK;
 }
@@ -2572,8 +2491,21 @@ static int finish_device_scan(hx_index *ix, const HxFusedView &v, uint32_t q0, u
 {
     const Graph &g = ix->g;
     const uint32_t ke = std::min<uint32_t>(limit, ef_search);
-    int rc;
     uint64_t cnts[2] = {0, 0};
+    // amgettuple for query q from result row src: every heap TID of each element, nearest first (scan.rs:794-875)
+    auto expand_tids = [&](uint32_t q, size_t src, const uint32_t *cnt, const uint32_t *ids, const float *d) {
+        uint32_t c = 0;
+        for (uint32_t i = 0; i < cnt[src] && c < limit; i++) {
+            const uint32_t el = ids[src * ke + i];
+            for (int t = (int)g.ntids[el] - 1; t >= 0 && c < limit; t--) {
+                tids_out[(size_t)q * limit + c] = g.tids[el][t];
+                if (dist_out) dist_out[(size_t)q * limit + c] = d[src * ke + i];
+                if (elems_out) elems_out[(size_t)q * limit + c] = el;
+                c++;
+            }
+        }
+        counts_out[q] = c;
+    };
     const uint32_t *status = v.status, *ocnt = v.cnt, *oids = v.ids; const float *od = v.d;
     const double t_exp0 = hx_index::now_s();
     ix->pool->parallel_for((nq + 1023) / 1024, [&](size_t ci) {
@@ -2582,47 +2514,21 @@ static int finish_device_scan(hx_index *ix, const HxFusedView &v, uint32_t q0, u
             if (q + 1 < nq) for (uint32_t i = 0; i < ocnt[q + 1] && i < ke; i++) {      // the heap TIDs of the next query's elements: random host reads
                 const uint32_t eln = oids[(size_t)(q + 1) * ke + i]; __builtin_prefetch(&g.tids[eln]); __builtin_prefetch(&g.ntids[eln]);
             }
-            uint32_t c = 0;                                  // amgettuple: every heap TID of each element, nearest first (scan.rs:794-875)
-            for (uint32_t i = 0; i < ocnt[q] && c < limit; i++) {
-                const uint32_t el = oids[(size_t)q * ke + i];
-                for (int t = (int)g.ntids[el] - 1; t >= 0 && c < limit; t--) {
-                    tids_out[(size_t)q * limit + c] = g.tids[el][t];
-                    if (dist_out) dist_out[(size_t)q * limit + c] = od[(size_t)q * ke + i];
-                    if (elems_out) elems_out[(size_t)q * limit + c] = el;
-                    c++;
-                }
-            }
-            counts_out[q] = c;
+            expand_tids(q, q, ocnt, oids, od);
         }
     });
     ix->prof[15] += hx_index::now_s() - t_exp0;
-    std::vector<uint32_t> again;                             // overflowed queries: one more try on the device with roomier tables
-    for (uint32_t q = 0; q < nq; q++) { if (status[q] == 1) again.push_back(q); else if (status[q] != 0) todo.push_back(q); }
-    if (!again.empty()) {
-        const uint32_t na = (uint32_t)again.size();
-        std::vector<uint32_t> q2(na);
-        for (uint32_t k = 0; k < na; k++) q2[k] = HX_QUERY_SLOT | (q0 + again[k]);
-        HxFusedView v2;
-        if ((rc = ix->e->fused_run(0, na, q2.data(), nullptr, ef_search, ke, (uint32_t)g.entry, g.level[g.entry],
-                                   nullptr, nullptr, nullptr, nullptr, cnts, nullptr, &v2, 8))) return ix->fail(rc, ix->e->err);
-        ix->counters[4] += cnts[0];
-        for (uint32_t k = 0; k < na; k++) {
-            const uint32_t q = again[k];
-            if (v2.status[k] != 0) { todo.push_back(q); continue; }
-            uint32_t c = 0;
-            for (uint32_t i = 0; i < v2.cnt[k] && c < limit; i++) {
-                const uint32_t el = v2.ids[(size_t)k * ke + i];
-                for (int t = (int)g.ntids[el] - 1; t >= 0 && c < limit; t--) {
-                    tids_out[(size_t)q * limit + c] = g.tids[el][t];
-                    if (dist_out) dist_out[(size_t)q * limit + c] = v2.d[(size_t)k * ke + i];
-                    if (elems_out) elems_out[(size_t)q * limit + c] = el;
-                    c++;
-                }
-            }
-            counts_out[q] = c;
-        }
-    }
-    return HX_OK;
+    return ix->retry_ladder(nq, v, true, [&](uint32_t q, size_t src, const HxFusedView &r) { expand_tids(q, src, r.cnt, r.ids, r.d); },
+        [&](const std::vector<uint32_t> &again, HxFusedView &v2) -> int {                // overflowed queries: one more try on the device with roomier tables
+            const uint32_t na = (uint32_t)again.size();
+            std::vector<uint32_t> q2(na);
+            for (uint32_t k = 0; k < na; k++) q2[k] = HX_QUERY_SLOT | (q0 + again[k]);
+            int rc = ix->e->fused_run(0, na, q2.data(), nullptr, ef_search, ke, (uint32_t)g.entry, g.level[g.entry],
+                                      nullptr, nullptr, nullptr, nullptr, cnts, nullptr, &v2, 8);
+            if (rc) return ix->fail(rc, ix->e->err);
+            ix->counters[4] += cnts[0];
+            return HX_OK;
+        }, todo);
 }
 
 static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, int64_t max_scan_tuples, uint32_t limit,
@@ -2651,7 +2557,6 @@ static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, 
         ix->prof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ix->counters[4] += cnts[0];
         if ((rc = finish_device_scan(ix, v, 0, nq, ef_search, limit, tids_out, dist_out, elems_out, counts_out, todo))) return rc;
-        ix->fused_tasks += nq; ix->fused_redo += todo.size();
         if (todo.empty()) return HX_OK;
     } else if (mode != 0 && ix->device_scan_ok() && ix->g.entry >= 0 && limit <= 4096) {
         // iterative scan on the device (k_fused MODE 2): the filter reaches the kernel as a per-element mask of passing heap TIDs
@@ -2688,34 +2593,37 @@ static int search_impl(hx_index *ix, uint32_t nq, uint32_t ef_search, int mode, 
                                    oids.data(), od.data(), ocnt.data(), status.data(), cnts, &it))) return ix->fail(rc, ix->e->err);
         ix->prof[6] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ix->counters[4] += cnts[0];
-        auto take = [&](uint32_t q, size_t src, const uint32_t *cn, const uint32_t *ids, const uint32_t *tix, const float *dd) {
-            const uint32_t c = std::min(cn[src], limit);
+        struct IterOut { const uint32_t *status = nullptr, *cnt = nullptr, *ids = nullptr, *tix = nullptr; const float *d = nullptr; };
+        auto take = [&](uint32_t q, size_t src, const IterOut &r) {
+            const uint32_t c = std::min(r.cnt[src], limit);
             for (uint32_t i = 0; i < c; i++) {
-                const uint32_t el = ids[src * limit + i];
-                tids_out[(size_t)q * limit + i] = g.tids[el][tix[src * limit + i]];
-                if (dist_out) dist_out[(size_t)q * limit + i] = dd[src * limit + i];
+                const uint32_t el = r.ids[src * limit + i];
+                tids_out[(size_t)q * limit + i] = g.tids[el][r.tix[src * limit + i]];
+                if (dist_out) dist_out[(size_t)q * limit + i] = r.d[src * limit + i];
                 if (elems_out) elems_out[(size_t)q * limit + i] = el;
             }
             counts_out[q] = c;
         };
-        std::vector<uint32_t> again;                             // scans that outgrew their visited table / discarded heap: once more on the device, 8x the room
-        for (uint32_t q = 0; q < nq; q++) {
-            if (status[q] == 1) again.push_back(q); else if (status[q] != 0) todo.push_back(q); else take(q, q, ocnt.data(), oids.data(), otix.data(), od.data());
-        }
-        if (!again.empty()) {
-            const uint32_t na = (uint32_t)again.size();
-            std::vector<uint32_t> q2(na), st2(na), c2(na), i2((size_t)na * limit), x2((size_t)na * limit); std::vector<float> d2((size_t)na * limit);
-            for (uint32_t k = 0; k < na; k++) q2[k] = HX_QUERY_SLOT | again[k];
-            std::vector<uint32_t> f2, k2;                   // the redone queries keep their filter row and predicate
-            if (it.t_frow) { f2.resize(na); for (uint32_t k = 0; k < na; k++) f2[k] = it.t_frow[again[k]]; }
-            if (it.t_key) { k2.resize(2 * (size_t)na); for (uint32_t k = 0; k < na; k++) { k2[2 * (size_t)k] = it.t_key[2 * (size_t)again[k]]; k2[2 * (size_t)k + 1] = it.t_key[2 * (size_t)again[k] + 1]; } }
-            HxFusedIter it2 = it; it2.out_tix = x2.data(); it2.t_frow = it.t_frow ? f2.data() : nullptr; it2.t_key = it.t_key ? k2.data() : nullptr;
-            if ((rc = ix->e->fused_run(2, na, q2.data(), nullptr, ef_search, limit, (uint32_t)g.entry, g.level[g.entry],
-                                       i2.data(), d2.data(), c2.data(), st2.data(), cnts, &it2, nullptr, 8))) return ix->fail(rc, ix->e->err);
-            ix->counters[4] += cnts[0];
-            for (uint32_t k = 0; k < na; k++) { if (st2[k] != 0) todo.push_back(again[k]); else take(again[k], k, c2.data(), i2.data(), x2.data(), d2.data()); }
-        }
-        ix->fused_tasks += nq; ix->fused_redo += todo.size();
+        IterOut first; first.status = status.data(); first.cnt = ocnt.data(); first.ids = oids.data(); first.tix = otix.data(); first.d = od.data();
+        std::vector<uint32_t> st2, c2, i2, x2, f2, k2; std::vector<float> d2;      // the relaunch's results and its tasks' filter rows / predicates
+        rc = ix->retry_ladder(nq, first, false, take,
+            [&](const std::vector<uint32_t> &again, IterOut &second) -> int {           // scans that outgrew their visited table / discarded heap: once more on the device, 8x the room
+                const uint32_t na = (uint32_t)again.size();
+                std::vector<uint32_t> q2(na);
+                st2.resize(na); c2.resize(na); i2.resize((size_t)na * limit); x2.resize((size_t)na * limit); d2.resize((size_t)na * limit);
+                for (uint32_t k = 0; k < na; k++) q2[k] = HX_QUERY_SLOT | again[k];
+                // the redone queries keep their filter row and predicate
+                if (it.t_frow) { f2.resize(na); for (uint32_t k = 0; k < na; k++) f2[k] = it.t_frow[again[k]]; }
+                if (it.t_key) { k2.resize(2 * (size_t)na); for (uint32_t k = 0; k < na; k++) { k2[2 * (size_t)k] = it.t_key[2 * (size_t)again[k]]; k2[2 * (size_t)k + 1] = it.t_key[2 * (size_t)again[k] + 1]; } }
+                HxFusedIter it2 = it; it2.out_tix = x2.data(); it2.t_frow = it.t_frow ? f2.data() : nullptr; it2.t_key = it.t_key ? k2.data() : nullptr;
+                int r = ix->e->fused_run(2, na, q2.data(), nullptr, ef_search, limit, (uint32_t)g.entry, g.level[g.entry],
+                                         i2.data(), d2.data(), c2.data(), st2.data(), cnts, &it2, nullptr, 8);
+                if (r) return ix->fail(r, ix->e->err);
+                ix->counters[4] += cnts[0];
+                second.status = st2.data(); second.cnt = c2.data(); second.ids = i2.data(); second.tix = x2.data(); second.d = d2.data();
+                return HX_OK;
+            }, todo);
+        if (rc) return rc;
         if (todo.empty()) return HX_OK;
     } else {
         for (uint32_t q = 0; q < nq; q++) todo.push_back(q);
@@ -2772,7 +2680,6 @@ int hx_index_search_wait(hx_index *ix, uint32_t slot, int64_t *tids_out, float *
     ix->counters[4] += cnts[0];
     std::vector<uint32_t> todo;
     if ((rc = finish_device_scan(ix, v, ss.first, ss.nq, ss.ef, ss.k, tids_out, dist_out, elems_out, counts_out, todo))) return rc;
-    ix->fused_tasks += ss.nq; ix->fused_redo += todo.size();
     if (todo.empty()) return HX_OK;
     // a query that outgrew even the roomy tables: the lock-step driver (still on the GPU kernels) serves it from its engine query slot
     return lockstep_scan(ix, todo, ss.first, ss.ef, 0, 0, ss.k, ScanWhere(), tids_out, dist_out, elems_out, counts_out);

@@ -958,3 +958,62 @@ def test_m_above_32_searches_in_the_traversal_kernel(dtype, metric, dim, n, m, e
         assert tids[q, :cnt[q]].tolist() == [t for t, _, _ in o.scan(qs[q], ef_search=40, limit=10)]
     ix.close()
     e.close()
+
+
+@pytest.mark.gpu
+def test_staged_batch_search_retries_overflowed_members_on_the_device():
+    """hx_index_batch_search (the staged, host-list form of a batch) on one rank with every 3rd member of a launch marked overflowed
+    (HX_FORCE_OVERFLOW_MOD): member 0, a retried member and an untouched member share each launch, the retried members' lists come from
+    the roomy relaunch, nothing reaches the lock-step driver and the graph is the oracle's."""
+    rng = np.random.default_rng(91)
+    n, dim, m, efc, batch = 600, 8, 8, 32, 96
+    rows = make_rows(hx.F32, n, dim, rng)
+    levels = hx.draw_levels(n, m, seed=9)
+    assert (levels > 0).any()
+    tids = np.arange(n, dtype=np.int64)
+    o, _ = build_oracle(hx.F32, hx.L2SQ, dim, rows, levels, m, efc, batch)
+    e = hx.Engine(hx.F32, hx.L2SQ, dim, n)
+    e.append(rows)
+    ix = hx.Index(e, m, efc)
+    os.environ["HX_FORCE_OVERFLOW_MOD"] = "3"
+    try:
+        done = 0
+        for b in hx.batch_schedule(0, n, batch):
+            if ix.entry < 0 or b < 16:
+                ix.insert(done, levels[done:done + b], tids[done:done + b], batch=b)
+            else:
+                ix.batch_begin(done, levels[done:done + b], tids[done:done + b])
+                ix.batch_search(0, b)
+                ix.batch_links(0, 1)
+                ix.batch_end(b)
+            done += b
+    finally:
+        del os.environ["HX_FORCE_OVERFLOW_MOD"]
+    st = ix.fused_stats()
+    assert st["redone"] == 0 and st["tasks"] > 0
+    assert_same_graph(ix, o, n)
+    ix.close()
+    e.close()
+
+
+@pytest.mark.gpu
+def test_m_above_32_members_left_by_the_device_finish_on_the_lock_step_driver():
+    """m > 32: the MODE 3 launch of a batch has no roomy retry, so with every 3rd member marked overflowed (HX_FORCE_OVERFLOW_MOD) those
+    members are searched and selected by the lock-step driver in the same hx_index_batch_search call that stores the others' lists from
+    k_select_w.  Same graph as the oracle's."""
+    rng = np.random.default_rng(40 * 7 + 24)
+    dtype, metric, dim, n, m, efc, batch = hx.F32, hx.L2SQ, 24, 400, 40, 80, 64
+    rows = make_rows(dtype, n, dim, rng)
+    rows[n // 2] = rows[3]
+    levels = hx.draw_levels(n, m, seed=19)
+    os.environ["HX_FORCE_OVERFLOW_MOD"] = "3"
+    try:
+        e, ix, elem, o, oelem = build_both(dtype, metric, dim, rows, levels, m, efc, batch, True)
+    finally:
+        del os.environ["HX_FORCE_OVERFLOW_MOD"]
+    assert elem.tolist() == oelem.tolist()
+    st = ix.fused_stats()
+    assert 0 < st["redone"] < st["tasks"]
+    assert_same_graph(ix, o, n)
+    ix.close()
+    e.close()
