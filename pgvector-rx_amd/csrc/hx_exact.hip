@@ -258,7 +258,6 @@ __global__ void k_exact_compact(const uint64_t *__restrict__ words, uint64_t n_w
     while (bits) { const int b = __builtin_ctzll(bits); out[pos++] = row0 + (uint32_t)(w * 64 + b); bits &= bits - 1; }
 }
 
-struct ExPlan { uint32_t Q, R, cap, S, per, nqb, cap2; };
 constexpr uint32_t EX_SEED_ROWS = 16384;                      // prefix of the rows whose top k seeds the sidecar path's shared thresholds
 
 template <class OP, int HOP, int LPR, int RIF, int Q>
@@ -534,27 +533,13 @@ int ex_search(hx_engine *e, int op, uint32_t first_query, uint32_t nq, uint64_t 
     }
     HX_HIP(e, hipSetDevice(e->device));
 
-    // plan: query tile Q (LDS budget), rows per round R, per-(query, slice) buffer cap, slices S (~1024 workgroups), queries per block
-    const uint32_t pitch = (uint32_t)e->pitch;
-    ExPlan p{};
-    if (e->dtype == HX_SPARSE) { p.Q = 1; p.R = EX_WAVES * 64; }
-    else {
-        p.Q = nq >= 16 && 16ull * pitch <= 64 * 1024 ? 16 : nq >= 4 && 4ull * pitch <= 64 * 1024 ? 4 : 1;
-        const uint32_t rif = p.Q == 16 ? 2 : 4, lpr = pitch > 128 ? 64 : 8;
-        p.R = EX_WAVES * rif * (64 / lpr);
-    }
-    p.cap = 64; while (p.cap < 2 * k || p.cap < k + p.R) p.cap <<= 1;
-    p.cap2 = 4096; while (p.cap2 < 4 * k) p.cap2 <<= 1;
-    const uint32_t tiles_all = (nq + p.Q - 1) / p.Q;
-    p.S = std::max<uint64_t>(1, std::min<uint64_t>((1024 + tiles_all - 1) / tiles_all, (n_pass + 4 * p.R - 1) / (4 * p.R)));
-    p.per = (uint32_t)((n_pass + p.S - 1) / p.S);
-    p.S = (uint32_t)((n_pass + p.per - 1) / p.per);
-    // top-k scratch per query: S buffers of cap entries + S counts + the merged output; bounded by HX_EXACT_SCRATCH bytes (default 256 MiB).
+    // plan (hx_exact_plan.h: ex_plan_plain): query tile Q, rows per round R, per-(query, slice) buffer cap, slices S, queries per block.
+    // The top-k scratch is bounded by HX_EXACT_SCRATCH bytes (default 256 MiB).
     // A filtered call also holds its bitmap (n_rows / 8 B) and the compacted id list (4 B per passing row) on the device.
+    const uint32_t pitch = (uint32_t)e->pitch;
     uint64_t budget = 256ull << 20;
     if (const char *env = getenv("HX_EXACT_SCRATCH")) budget = std::max<uint64_t>(1, strtoull(env, nullptr, 10));
-    const uint64_t per_q = (uint64_t)p.S * p.cap * 12 + (uint64_t)p.S * 4 + (uint64_t)k * 12 + 4;
-    p.nqb = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(p.Q, budget / per_q / p.Q * p.Q));
+    const ExPlan p = ex_plan_plain(nq, pitch, e->dtype == HX_SPARSE, n_pass, k, budget);
 
     const size_t ids_bytes = row_pass ? al16((size_t)n_pass * 4) : 0, words_bytes = row_pass ? al16((size_t)n_words * 8) : 0;
     const size_t o_words = ids_bytes, o_ctr = o_words + words_bytes, o_key = o_ctr + 16;

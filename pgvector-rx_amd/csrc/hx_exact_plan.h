@@ -1,6 +1,7 @@
-// hx_exact_plan.h -- the host plan of hx_exact_search_filtered's grouped path (hx_exact.hip): queries grouped by their filter, every group
-// cut into query tiles, every tile into row slices, one work descriptor per scan workgroup and one per query for the merge.
-// Plain C++ with no device code: tests/test_exact_plan_host.py compiles it into a stand-alone program.
+// hx_exact_plan.h -- the host plans of the exact top-k scans (hx_exact.hip).  ex_plan: hx_exact_search_filtered's grouped path, queries grouped
+// by their filter, every group cut into query tiles, every tile into row slices, one work descriptor per scan workgroup and one per query for
+// the merge.  ex_plan_plain: hx_exact_search's tile size, slices and query blocks.
+// Plain C++ with no device code: tests/test_exact_plan_host.py and tests/test_exact_steady_plan.py compile it into stand-alone programs.
 //
 // Input: the groups in the order their queries stand in the grouped query order (ex_plan's positions 0 .. sum of nq - 1), each with its
 //   number of queries (> 0), its number of passing rows (> 0) and where its row-id list starts (EX_NO_IDS: the plain row range).
@@ -57,6 +58,27 @@ inline uint32_t ex_plan_rows_per_round(uint32_t Q, uint32_t pitch, bool sparse)
 {
     if (sparse) return 4 * 64;
     return 4 * (Q == 16 ? 2 : 4) * (pitch > 128 ? 1 : 8);
+}
+
+// The plan of the plain call (hx_exact_search; one filter or none for all nq queries, n_pass passing rows): query tile Q (LDS budget), rows
+// per round R, per-(query, slice) buffer cap, slices S (~1024 workgroups, at least four rounds each), queries per block nqb (scratch budget).
+struct ExPlan { uint32_t Q, R, cap, S, per, nqb, cap2; };
+
+inline ExPlan ex_plan_plain(uint32_t nq, uint32_t pitch, bool sparse, uint64_t n_pass, uint32_t k, uint64_t budget)
+{
+    ExPlan p{};
+    p.Q = sparse ? 1 : nq >= 16 && 16ull * pitch <= 64 * 1024 ? 16 : nq >= 4 && 4ull * pitch <= 64 * 1024 ? 4 : 1;
+    p.R = ex_plan_rows_per_round(p.Q, pitch, sparse);
+    p.cap = 64; while (p.cap < 2 * k || p.cap < k + p.R) p.cap <<= 1;
+    p.cap2 = 4096; while (p.cap2 < 4 * k) p.cap2 <<= 1;
+    const uint32_t tiles_all = (nq + p.Q - 1) / p.Q;
+    p.S = std::max<uint64_t>(1, std::min<uint64_t>((1024 + tiles_all - 1) / tiles_all, (n_pass + 4 * p.R - 1) / (4 * p.R)));
+    p.per = (uint32_t)((n_pass + p.S - 1) / p.S);
+    p.S = (uint32_t)((n_pass + p.per - 1) / p.per);
+    // top-k scratch per query: S buffers of cap entries + S counts + the merged output
+    const uint64_t per_q = (uint64_t)p.S * p.cap * 12 + (uint64_t)p.S * 4 + (uint64_t)k * 12 + 4;
+    p.nqb = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(p.Q, budget / per_q / p.Q * p.Q));
+    return p;
 }
 
 inline ExGPlan ex_plan(const std::vector<ExGroup> &groups, uint32_t k, uint32_t pitch, bool sparse, uint64_t budget)

@@ -17,8 +17,9 @@ def self_ip(dtype, dim, rows):
 def values(dtype, dim, op, q, rows, row_norms=None):
     """Operator values of query q against every row of `rows` (f64)."""
     if dtype == orc.SPARSE and op == hx.OP_COSINE:
-        L, qa = orc.lib(), orc.as_rows(dtype, q)
-        return np.array([L.orc_cosine_distance(dtype, dim, orc._p(qa), orc._p(orc.as_rows(dtype, r))) for r in rows], np.float64)
+        L, qa, ra = orc.lib(), orc.as_rows(dtype, q), orc.as_rows(dtype, rows)       # one record per row: addressed in place
+        fn, qp, base, rb = L.orc_cosine_distance, orc._p(qa), ra.ctypes.data, ra.nbytes // max(len(ra), 1)
+        return np.array([fn(dtype, dim, qp, base + i * rb) for i in range(len(ra))], np.float64)
     if op == hx.OP_COSINE:
         s = -orc.distances_many(dtype, orc.NEG_IP, dim, q, rows, order=orc.W64)
         na = self_ip(dtype, dim, rows) if row_norms is None else row_norms
